@@ -18,15 +18,23 @@ value = aggregate GEMM TFLOP/s over all N GPUs (weak scaling: per-GPU work is
 fixed). Synthetic U[-1,1) operands (random data, not zeros: DVFS reads zeros
 fast, cdna_hip_programming.md rule 25).
 
-Self-normalising and self-checking (after the timed region, which alone gives
-``value`` and ``ms_per_step``): the last timed GEMM's whole output is compared
-with an fp32 reference (``rel_err``; the run fails above ``--max-rel-err``),
-and ``--yardstick-rounds`` interleaved rounds of S kgs steps and S steps of the
-same workload on the vendor GEMM (torch.matmul -> hipBLASLt) give
-``hipblaslt_tflops`` and ``ratio_vs_hipblaslt`` on the same box, so a change in
-``value`` between runs reads as box speed or kernel change.
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, write the outputs (``--dump-outputs``) and print the result line.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+``--full`` adds the self-normalising, self-checking part (after the timed
+region, which alone gives ``value`` and ``ms_per_step``): the last timed GEMM's
+whole output is compared with an fp32 reference (``rel_err``; the run fails
+above ``--max-rel-err``), and ``--yardstick-rounds`` interleaved rounds of S kgs
+steps and S steps of the same workload on the vendor GEMM (torch.matmul ->
+hipBLASLt) give ``hipblaslt_tflops`` and ``ratio_vs_hipblaslt`` on the same
+box, so a change in ``value`` between runs reads as box speed or kernel change.
+
+``--dump-outputs DIR`` writes what the last timed step computed (the GEMM
+output buffers a caller of the step receives) as ``DIR/<name>.npy`` in float32:
+whole when small, else a fixed seeded sample of elements. Operands are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         torchrun --nproc-per-node N bench.py --gpus N ...
 
 With ``--gpus N > 1`` and no WORLD_SIZE in the environment the script launches
@@ -70,12 +78,19 @@ def parse(argv=None):
     ap.add_argument("--allreduce-mb", type=float, default=64.0, help="gradient bucket all-reduced per step (MiB)")
     ap.add_argument("--no-overlap", action="store_true", help="run the all-reduce after the GEMMs, same stream")
     ap.add_argument("--compare-torch", action="store_true", help="also time torch.matmul (hipBLASLt), untimed part")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also check the last timed output against fp32 (rel_err, "
+                         "--max-rel-err) and time the same-box vendor-GEMM yardstick (--yardstick-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's GEMM outputs as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of a large output)")
     ap.add_argument("--yardstick-rounds", type=int, default=3,
-                    help="after the timed region: this many interleaved rounds of (S kgs steps, S vendor-GEMM "
-                         "steps) on the same operands, medians -> ratio_vs_hipblaslt (0 = off)")
+                    help="with --full, after the timed region: this many interleaved rounds of (S kgs steps, S "
+                         "vendor-GEMM steps) on the same operands, medians -> ratio_vs_hipblaslt (0 = off)")
     ap.add_argument("--yardstick-steps", type=int, default=20, help="S, steps per yardstick block")
     ap.add_argument("--max-rel-err", type=float, default=1e-2,
-                    help="the last timed GEMM's whole output is checked against fp32; above this the run fails")
+                    help="with --full the last timed GEMM's whole output is checked against fp32; above this the "
+                         "run fails")
     ap.add_argument("--verify", action="store_true", help="check one GEMM against fp32 torch before timing")
     ap.add_argument("--backend", choices=("kgs", "torch"), default="kgs",
                     help="kgs = hand-written gfx950 kernel (the benchmark); torch = reference / CPU test path")
@@ -182,6 +197,29 @@ def yardstick(wl, ctx, sync, rounds: int, steps: int) -> dict:
             "ref_ms": [round(t, 4) for t in ref]}
 
 
+DUMP_SAMPLE = 4 << 20  # elements per dumped array above which a sample is written (16 MiB of float32)
+DUMP_SEED = 20240  # fixes the sampled element indices, the same for every run and build
+
+
+def dump_outputs(wl, outdir: str, rank: int) -> None:
+    """Write the output buffers the last timed step left (every ``C`` the
+    step's GEMMs wrote) as ``<outdir>/c<i>.npy`` in float32 (``c<i>_rank<r>``
+    on ranks > 0). An output of more than ``DUMP_SAMPLE`` elements is written
+    as its elements at ``DUMP_SAMPLE`` sorted flat indices drawn once from a
+    generator seeded with ``DUMP_SEED``."""
+    import numpy as np
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    for i in sorted({j & 1 for j in range(wl.g)}):  # the buffers this step wrote
+        c = wl.c[i].reshape(-1)
+        if c.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, c.numel(), size=DUMP_SAMPLE))
+            c = c[torch.from_numpy(idx).to(c.device)]
+        name = f"c{i}" if rank == 0 else f"c{i}_rank{rank}"
+        np.save(os.path.join(outdir, name + ".npy"), c.float().cpu().numpy())
+
+
 def run(args, wd) -> int:
     import torch
     from kgs.models.gemm_workload import GemmWorkload
@@ -244,13 +282,17 @@ def run(args, wd) -> int:
     sync()
     elapsed = time.perf_counter() - t0
     elapsed_max = kdist.max_over_ranks(ctx, elapsed)
-    # --- untimed from here: the check and the same-box yardstick ---
-    wd.set_phase("check")
-    rel_err = kdist.max_over_ranks(ctx, wl.check_output())
-    ys = None
-    if args.yardstick_rounds > 0 and rel_err <= args.max_rel_err:
-        wd.set_phase("yardstick")
-        ys = yardstick(wl, ctx, sync, args.yardstick_rounds, args.yardstick_steps)
+    # --- untimed from here: the dump, and with --full the check and the same-box yardstick ---
+    if args.dump_outputs:
+        wd.set_phase("dump")
+        dump_outputs(wl, args.dump_outputs, rank)
+    rel_err = ys = None
+    if args.full:
+        wd.set_phase("check")
+        rel_err = kdist.max_over_ranks(ctx, wl.check_output())
+        if args.yardstick_rounds > 0 and rel_err <= args.max_rel_err:
+            wd.set_phase("yardstick")
+            ys = yardstick(wl, ctx, sync, args.yardstick_rounds, args.yardstick_steps)
     wd.set_phase("report")
 
     per_rank_ms = [round(t / max(1, args.steps) * 1e3, 4) for t in kdist.all_gather_object(ctx, elapsed)]
@@ -268,14 +310,15 @@ def run(args, wd) -> int:
         extra["allreduce_busbw_gbs"] = round(ar_bytes / (ar_ms * 1e-3) * 2 * (world - 1) / world / 1e9, 2)
     if args.compare_torch:
         extra["torch_matmul_tflops_per_gpu"] = round(wl.torch_reference_tflops(), 1)
-    extra["rel_err"] = float(f"{rel_err:.3e}")
+    if rel_err is not None:
+        extra["rel_err"] = float(f"{rel_err:.3e}")
     if ys is not None:
         kgs_ms, ref_ms = ys["kgs_ms_per_step"], ys["ref_ms_per_step"]
         extra["hipblaslt_tflops"] = round(flops_per_step / (ref_ms * 1e-3) / 1e12 * world, 2)
         extra["ratio_vs_hipblaslt"] = round(ref_ms / kgs_ms, 4)  # > 1: the kgs step is faster
         extra["yardstick"] = {**ys, "path": wl.reference_path_name(),
                               "kgs_tflops": round(flops_per_step / (kgs_ms * 1e-3) / 1e12 * world, 2)}
-    if rel_err > args.max_rel_err:
+    if rel_err is not None and rel_err > args.max_rel_err:
         if rank == 0:
             launch.report_once({**error_report(args, world), "status": "error", "exit_code": 1, "phase": "check",
                                 "rel_err": rel_err, "reason": f"timed GEMM output rel err {rel_err:.3e} > "

@@ -14,7 +14,7 @@
 # Steps:
 #   tests        full GPU pytest tier (per-test thread timeout)
 #   smoke        __graft_entry__.smoke()
-#   bench        python bench.py (driver defaults)
+#   bench        python bench.py --full (driver defaults, with the fp32 check and the hipBLASLt yardstick)
 #   bench_long   sustained >=10 s run of the bench config (steps=400)
 #   gemm_sweep   kgs vs hipBLASLt interleaved sweep of the headline shapes
 #   gemm_trace   rocprofv3 kernel trace + stats of the GEMM profile driver
@@ -64,7 +64,7 @@
 #   serve_b16    batch-16 serving; skinny_tune: skinny GEMM variant x split-K tune at batches $MS
 #   online_sweep online serving (Poisson arrivals, 2048-row chunked steps) at 8-96 req/s
 #   serve_sweep  offline serving at batch 1 / 64 / 128 / 256 / 512, fp8 KV, fp8 prefill + fp8 KV (256 and 512)
-#   bench_fp8    bench.py --dtype fp8 (e4m3 operands, extra)
+#   bench_fp8    bench.py --full --dtype fp8 (e4m3 operands, extra)
 #   stages_probe LDS stages x tiles on the four decode projections
 #   route_ab     128-row decode tiles probe, then serve_ab; serve_ab: batch-256 serving A/B/A with
 #                $AENV / $BENV (one VAR=value each) and $ROUTES (KGS_W4X_ROUTES), trace of B
@@ -96,9 +96,9 @@ step() {
         tests) KGS_EVIDENCE_DIR="$O" run tests 1100 python -u -m pytest tests -x -v -m gpu --timeout 120 \
             --timeout-method thread ;;
         smoke) run smoke 300 python __graft_entry__.py smoke ;;
-        bench) run bench 300 python bench.py ;;
-        bench_long) run bench_long 300 python bench.py --steps 4000 --warmup 20 ;;
-        bench_fp8) run bench_fp8 300 python bench.py --dtype fp8 ;;
+        bench) run bench 300 python bench.py --full ;;
+        bench_long) run bench_long 300 python bench.py --full --steps 4000 --warmup 20 ;;
+        bench_fp8) run bench_fp8 300 python bench.py --full --dtype fp8 ;;
         gemm_sweep) run gemm_sweep 600 python bench/gemm_sweep.py --shapes 4096,8192,16384x16384x8192 \
             --variants fast --rounds 7 --out "$O/gemm_sweep.json" ;;
         gemm_trace) run gemm_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o gemm \
@@ -254,7 +254,7 @@ step() {
             run ws_sum 60 python3 bench/wait_split.py --summary "$O/ws_sq" --plan $O/ws_plan.json \
                 --json "$O/wait_split.json" ;;
         bench_trace) run bench_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/btrace" -o b \
-            -- python3 bench.py --steps 20 --warmup 5 ;;
+            -- python3 bench.py --full --steps 20 --warmup 5 ;;
         overlap_rccl) run overlap_rccl 300 python bench/overlap_rccl.py --out "$O/overlap_rccl_shape.json" &&
             run overlap_rccl_hi 300 python bench/overlap_rccl.py --side-priority high \
                 --out "$O/overlap_rccl_shape_hiprio.json" ;;

@@ -487,13 +487,13 @@ def _bench_inproc(*extra):
 
 
 def test_bench_line_carries_same_box_yardstick_and_full_check(monkeypatch):
-    """the default run checks the last timed output in full
+    """the --full run checks the last timed output in full
     against fp32 (rel_err) and times the vendor GEMM interleaved with the kgs
     step (hipblaslt_tflops, ratio_vs_hipblaslt). value / ms_per_step stay the
     timed region's: value = 4 GEMMs x 2MNK / ms_per_step."""
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
-    rc, j = _bench_inproc()
+    rc, j = _bench_inproc("--full")
     assert rc == 0 and "status" not in j
     for key in ("rel_err", "hipblaslt_tflops", "ratio_vs_hipblaslt", "yardstick"):
         assert key in j, key
@@ -505,8 +505,58 @@ def test_bench_line_carries_same_box_yardstick_and_full_check(monkeypatch):
     assert j["value"] == pytest.approx(flops / (j["ms_per_step"] * 1e-3) / 1e12, abs=0.011, rel=2e-3)
     # the yardstick is untimed extra: its kgs median is not what value reports
     assert j["ms_per_step"] == max(j["per_rank_ms_per_step"])
-    rc0, j0 = _bench_inproc("--yardstick-rounds", "0")
+    rc0, j0 = _bench_inproc("--full", "--yardstick-rounds", "0")
     assert rc0 == 0 and "ratio_vs_hipblaslt" not in j0 and "rel_err" in j0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(monkeypatch, tmp_path):
+    """Without --full the line keeps the headline fields and carries neither the
+    fp32 check nor the yardstick; --dump-outputs writes the last timed step's
+    GEMM outputs as float32 .npy, identical from run to run and equal to
+    A . B^T of the seeded operands."""
+    import numpy as np
+
+    from kgs.models.gemm_workload import GemmWorkload
+
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    rc, j = _bench_inproc("--dump-outputs", str(tmp_path / "a"))
+    assert rc == 0 and "status" not in j
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in j, key
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+    for key in ("rel_err", "hipblaslt_tflops", "ratio_vs_hipblaslt", "yardstick"):
+        assert key not in j, key
+    rc, _ = _bench_inproc("--dump-outputs", str(tmp_path / "b"))
+    assert rc == 0
+    assert sorted(os.listdir(tmp_path / "a")) == ["c0.npy", "c1.npy"] == sorted(os.listdir(tmp_path / "b"))
+    wl = GemmWorkload(m=128, n=64, k=96, device="cpu", seed=1234, backend="torch")
+    ref = (wl.a.float() @ wl.b.float().T).bfloat16().float().numpy()
+    for name in ("c0.npy", "c1.npy"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and a.shape == (128 * 64,)
+        assert np.array_equal(a, b)
+        # one bf16 ulp (2^-8 relative) for the rounding of C; fp32 sums of 96 terms below 1 differ by < 1e-5
+        np.testing.assert_allclose(a.reshape(128, 64), ref, rtol=2 ** -7, atol=1e-5)
+
+
+def test_bench_dump_samples_a_large_output(monkeypatch, tmp_path):
+    """An output above bench.DUMP_SAMPLE elements is written as a fixed seeded
+    sample: the same elements in every run, each equal to the output there."""
+    import numpy as np
+
+    import bench
+    from kgs.models.gemm_workload import GemmWorkload
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    wl = GemmWorkload(m=128, n=64, k=96, gemms_per_step=1, device="cpu", seed=3, backend="torch")
+    wl.step()
+    bench.dump_outputs(wl, str(tmp_path), rank=0)
+    assert os.listdir(tmp_path) == ["c0.npy"]  # one GEMM per step writes only the first buffer
+    got = np.load(tmp_path / "c0.npy")
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 128 * 64, size=1000))
+    assert got.dtype == np.float32 and got.shape == (1000,)
+    assert np.array_equal(got, wl.c[0].float().numpy().reshape(-1)[idx])
 
 
 def test_bench_fails_loudly_on_a_wrong_timed_output(monkeypatch):
@@ -521,6 +571,6 @@ def test_bench_fails_loudly_on_a_wrong_timed_output(monkeypatch):
         if not reference:
             self.c[(self.g - 1) & 1][3, 5] += 1e3  # one wrong element in the timed output
     monkeypatch.setattr(GemmWorkload, "step", corrupt)
-    rc, j = _bench_inproc()
+    rc, j = _bench_inproc("--full")
     assert rc == 1
     assert j["status"] == "error" and j["phase"] == "check" and j["rel_err"] > 1e-2 and j["value"] is None
