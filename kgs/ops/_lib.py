@@ -76,6 +76,9 @@ _SIGS = {
                              _c_int),
     "kgs_attn_fwd_bf16": ([_c_void_p] * 4 + [_c_int] * 5 + [_c_long] * 4 + [ctypes.c_float, _c_int, _c_void_p],
                           _c_int),
+    # paged prefill attention (native/kernels/attention_paged.hip)
+    "kgs_attn_prefill_paged_bf16": ([_c_void_p] * 6 + [_c_int] * 6 + [_c_long] * 2 + [ctypes.c_float, _c_void_p],
+                                    _c_int),
     # decode path (native/kernels/decode.hip)
     "kgs_skinny_geometry": ([_c_int, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)], _c_int),
     "kgs_skinny_gemm_bf16": ([_c_void_p] * 5 + [_c_int] * 3 + [_c_long, _c_long, _c_int, _c_void_p], _c_int),

@@ -12,6 +12,9 @@ tests compare them with.
   :func:`kgs.ops.gemm.gemm_fp8_rows` (W8A8, per-token dynamic activation scales)
 * :func:`attention_qkv` -- causal/full GQA flash attention (head_dim 128) reading
   q, k, v straight out of the fused QKV buffer and writing ``[tokens, H*128]``
+* :func:`paged_prefill_plan`, :func:`paged_prefill_attention` -- every prompt
+  chunk of a chunked-prefill step in one launch, keys / values read in place
+  from the bf16 KV pages (``native/kernels/attention_paged.hip``)
 
 Every op raises :class:`kgs.ops.NativeUnavailable` when the native library is
 missing -- there is no silent PyTorch fallback.
@@ -224,6 +227,136 @@ def attention_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
                                          float(scale), 1, _lib.stream_handle(q.device))
     _lib.check(rc, "attention_chunk")
     return out
+
+
+class PagedPrefillPlan:
+    """One step's prompt chunks as :func:`paged_prefill_attention` takes them
+    (built by :func:`paged_prefill_plan`, shared by every layer of the step):
+    ``chunks`` the host list of ``(row0, n, padded, ctx0)``, ``desc`` the same as
+    int32 ``[nchunks, 4]`` on the device, ``qmap`` int32 ``[nqb, 2]`` mapping a
+    q-block to ``(chunk, q-block in chunk)`` heaviest first, ``block_tables``
+    int32 ``[nchunks, max_pages]``, ``rows`` one past the last Q row any chunk
+    touches, ``max_page`` the largest page index in the tables (None when they
+    were handed over on the device: reading them back would synchronise)."""
+
+    __slots__ = ("chunks", "desc", "qmap", "block_tables", "rows", "max_page")
+
+    def __init__(self, chunks, desc, qmap, block_tables, rows, max_page):
+        self.chunks, self.desc, self.qmap, self.block_tables = chunks, desc, qmap, block_tables
+        self.rows, self.max_page = rows, max_page
+
+
+_PP_QB, _PP_KB, _PP_PAGE = 128, 64, 32  # attention_paged.hip: q-block rows, keys per tile, tokens per page
+
+
+def paged_prefill_plan(chunks, block_tables, device) -> PagedPrefillPlan:
+    """Validate one step's prompt chunks and build what the paged prefill
+    kernel reads, once per step. ``chunks``: host ``(row0, n, padded, ctx0)`` per
+    chunk -- Q rows ``row0 .. row0+padded-1`` hold positions ``ctx0 ..
+    ctx0+padded-1``, ``n`` of them real; ``block_tables``: ``[nchunks, max_pages]``
+    (an int tensor on any device, or nested lists), entries ``0 ..
+    ceil((ctx0+n)/32)-1`` of a row the sequence's pages and every later entry a
+    valid page index. Raises ``ValueError`` naming the offending chunk."""
+    chunks = [tuple(int(v) for v in ch[:4]) for ch in chunks]
+    if not chunks:
+        raise ValueError("paged_prefill_plan: no chunks")
+    bt = block_tables if isinstance(block_tables, torch.Tensor) else torch.as_tensor(block_tables, dtype=torch.int32)
+    if bt.dim() != 2 or bt.shape[0] != len(chunks) or bt.shape[1] < 1:
+        raise ValueError(f"block_tables must be [nchunks = {len(chunks)}, max_pages], got {tuple(bt.shape)}")
+    width = bt.shape[1]
+    work = []
+    for ci, ch in enumerate(chunks):
+        row0, n, padded, ctx0 = ch
+        if row0 < 0 or padded <= 0 or padded % _PP_QB:
+            raise ValueError(f"chunk {ci} {ch}: padded must be a positive multiple of {_PP_QB} (and row0 >= 0)")
+        if ctx0 < 0 or ctx0 % _PP_KB:
+            raise ValueError(f"chunk {ci} {ch}: ctx0 must be a non-negative multiple of {_PP_KB}")
+        if not 1 <= n <= padded:
+            raise ValueError(f"chunk {ci} {ch}: need 1 <= n <= padded")
+        need = -(-(ctx0 + n) // _PP_PAGE)
+        if width < need:
+            raise ValueError(f"chunk {ci} {ch}: block table holds {width} pages, the chunk's context needs {need}")
+        nreal = -(-(ctx0 + n) // _PP_KB)
+        for qb in range(padded // _PP_QB):
+            tiles = 0 if qb * _PP_QB >= n else min((ctx0 + (qb + 1) * _PP_QB) // _PP_KB, nreal)
+            work.append((tiles, ci, qb))
+    work.sort(key=lambda t: -t[0])  # heaviest first (stable: equal weights keep chunk order)
+    max_page = None
+    if bt.device.type == "cpu":
+        if int(bt.min()) < 0:
+            raise ValueError("block_tables holds a negative page index")
+        max_page = int(bt.max())
+    dev = torch.device(device)
+    host = torch.tensor([v for ch in chunks for v in ch] + [v for _, ci, qb in work for v in (ci, qb)],
+                        dtype=torch.int32)
+    if dev.type == "cuda":
+        host = host.pin_memory().to(dev, non_blocking=True)
+    nd = 4 * len(chunks)
+    bt = bt.to(device=dev, dtype=torch.int32).contiguous()
+    return PagedPrefillPlan(chunks, host[:nd].view(len(chunks), 4), host[nd:].view(len(work), 2), bt,
+                            max(ch[0] + ch[2] for ch in chunks), max_page)
+
+
+def paged_prefill_attention(qkv: torch.Tensor, cache_layer: torch.Tensor, plan: PagedPrefillPlan, heads: int,
+                            kv_heads: int, out: torch.Tensor | None = None, scale: float | None = None
+                            ) -> torch.Tensor:
+    """Causal flash attention of every prompt chunk of ``plan`` in ONE launch,
+    keys and values read in place from ``cache_layer`` (one layer of a bf16
+    :class:`kgs.ops.decode.PagedKVCache`, which already holds the chunks' own
+    rows). ``qkv``: the fused, rotated QKV rows (the q heads are read). Row ``r <
+    n`` of a chunk sees keys ``0 .. ctx0+r``; rows ``>= n`` come back as zeros;
+    rows of ``out`` ``[rows, heads*128]`` outside every chunk are left alone.
+    Call once per layer with the step's plan."""
+    _need(qkv, "qkv")
+    if cache_layer.dtype != torch.bfloat16:
+        raise TypeError("paged_prefill_attention reads bf16 KV pages (an fp8 cache keeps the gather path)")
+    if not cache_layer.is_cuda or cache_layer.dim() != 4 or not cache_layer.is_contiguous() or \
+            tuple(cache_layer.shape[1:]) != (kv_heads, 2, _PP_PAGE * 128):
+        raise ValueError("cache_layer must be a contiguous GPU [pages, kv_heads, 2, 4096] page array")
+    if heads % kv_heads or qkv.shape[1] < heads * 128:
+        raise ValueError("qkv rows must hold heads * 128 q elements, heads a multiple of kv_heads")
+    if plan.rows > qkv.shape[0]:
+        raise ValueError(f"the plan's chunks reach row {plan.rows}, qkv has {qkv.shape[0]}")
+    if plan.max_page is not None and plan.max_page >= cache_layer.shape[0]:
+        raise ValueError(f"block table entry {plan.max_page} outside the cache's {cache_layer.shape[0]} pages")
+    if plan.desc.device != qkv.device:
+        raise ValueError("the plan was built for another device")
+    out = torch.empty((qkv.shape[0], heads * 128), dtype=torch.bfloat16, device=qkv.device) if out is None else out
+    _need(out, "out")
+    if out.shape[0] < plan.rows or out.shape[1] < heads * 128:
+        raise ValueError("out must be [>= rows of the plan, >= heads*128]")
+    scale = 1.0 / math.sqrt(128) if scale is None else scale
+    rc = _lib.lib().kgs_attn_prefill_paged_bf16(qkv.data_ptr(), cache_layer.data_ptr(), plan.block_tables.data_ptr(),
+                                                plan.desc.data_ptr(), plan.qmap.data_ptr(), out.data_ptr(),
+                                                len(plan.chunks), plan.qmap.shape[0], heads, kv_heads, 128,
+                                                plan.block_tables.shape[1], qkv.stride(0), out.stride(0),
+                                                float(scale), _lib.stream_handle(qkv.device))
+    _lib.check(rc, "paged_prefill_attention")
+    return out
+
+
+def ref_paged_prefill_attention(qkv, cache_layer, plan, heads, kv_heads, out=None, scale=None):
+    """fp32 reference of :func:`paged_prefill_attention` (CPU or GPU tensors):
+    per chunk, the context through :func:`kgs.ops.decode.ref_gather_kv` and a
+    plain softmax(q k^T) v; rows ``>= n`` zero. Returns fp32 ``[rows, heads*128]``."""
+    from .decode import ref_gather_kv
+
+    scale = 1.0 / math.sqrt(128) if scale is None else scale
+    res = torch.zeros((qkv.shape[0], heads * 128), dtype=torch.float32, device=qkv.device)
+    rep = heads // kv_heads
+    for ci, (row0, n, _, ctx0) in enumerate(plan.chunks):
+        k, v = ref_gather_kv(cache_layer, plan.block_tables[ci], ctx0 + n)  # [ctx0+n, HKV, 128] fp32
+        k, v = k.repeat_interleave(rep, dim=1), v.repeat_interleave(rep, dim=1)
+        q = qkv[row0:row0 + n, :heads * 128].float().reshape(n, heads, 128)
+        s = torch.einsum("qhd,khd->hqk", q, k) * scale
+        dev = qkv.device
+        seen = torch.arange(ctx0 + n, device=dev)[None, :] <= (ctx0 + torch.arange(n, device=dev))[:, None]
+        p = torch.softmax(s.masked_fill(~seen, float("-inf")), dim=-1)
+        res[row0:row0 + n] = torch.einsum("hqk,khd->qhd", p, v).reshape(n, heads * 128)
+    if out is not None:
+        out[:res.shape[0]].copy_(res)
+        return out
+    return res
 
 
 def ref_attention_chunk(q, k, v, heads, kv_heads, head_dim=128, scale=None):

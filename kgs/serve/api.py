@@ -384,6 +384,9 @@ def main(argv=None) -> int:
     ap.add_argument("--chunked-prefill", type=int, default=2048,
                     help="rows per mixed prompt-chunk + decode step (0 = whole-prompt prefill steps)")
     ap.add_argument("--prefix-caching", action="store_true", help="reuse cached pages of shared prompt prefixes")
+    ap.add_argument("--paged-prefill", action="store_true",
+                    help="mixed steps: one paged prefill-attention launch per layer for all prompt chunks, reading "
+                         "the bf16 KV pages in place (no gather); not with --kv-cache-dtype fp8")
     ap.add_argument("--overlap", action=argparse.BooleanOptionalAction, default=False,
                     help="overlapped engine steps: ~7 %% lower TPOT for a few ms more TTFT (a request arriving "
                          "while a step is in flight misses that step; profiles/r5/overlap/README.md)")
@@ -408,7 +411,7 @@ def main(argv=None) -> int:
     ec = EngineConfig(max_batch=a.max_batch, max_model_len=a.max_model_len, cuda_graphs=not a.no_graphs,
                       chunked_prefill=a.chunked_prefill, prefix_caching=a.prefix_caching,
                       kv_cache_dtype=a.kv_cache_dtype, decode_weights=a.decode_weights,
-                      prefill_weights=a.prefill_weights, overlap=a.overlap)
+                      prefill_weights=a.prefill_weights, overlap=a.overlap, paged_prefill=a.paged_prefill)
     if a.data_parallel > 1 or a.engine_process:
         import dataclasses
 

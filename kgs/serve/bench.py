@@ -48,7 +48,8 @@ def run_engine(a) -> dict:
                       chunked_prefill=a.chunked_prefill, prefix_caching=a.prefix_caching,
                       packed_decode=not a.no_packed_decode, prefill_weights=a.prefill_weights,
                       fuse_splitk=not a.no_fuse_splitk, w4x_panels=not a.no_w4x_panels,
-                      gate_up_panels=not a.no_gate_up_panels, overlap=a.overlap != "off")
+                      gate_up_panels=not a.no_gate_up_panels, overlap=a.overlap != "off",
+                      paged_prefill=a.paged_prefill)
     t0 = time.perf_counter()
     eng = LLMEngine(mc, ec, device="cuda", backend="kgs")
     t_load = time.perf_counter() - t0
@@ -93,7 +94,7 @@ def run_engine(a) -> dict:
         "fuse_splitk": not a.no_fuse_splitk, "w4x_panels": not a.no_w4x_panels,
         "gate_up_panels": eng.model.gate_up_panels is not None, "overlap": eng.overlap,
         "nt_weights": NT_WEIGHTS,
-        "chunked_prefill": a.chunked_prefill,
+        "chunked_prefill": a.chunked_prefill, "paged_prefill": a.paged_prefill,
         "prefix_caching": a.prefix_caching, "shared_prefix": a.shared_prefix,
         "prefix_hit_tokens": int(eng.sched.prefix_hit_tokens),
         "seconds": round(dt, 3), "output_tok_per_s": round(n_out / dt, 1),
@@ -127,6 +128,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
                       decode_weights=a.decode_weights, kv_cache_dtype=a.kv_cache_dtype,
                       chunked_prefill=getattr(a, "chunked_prefill", 0),
                       prefix_caching=getattr(a, "prefix_caching", False),
+                      paged_prefill=getattr(a, "paged_prefill", False),
                       packed_decode=not getattr(a, "no_packed_decode", False),
                       overlap=getattr(a, "overlap", "auto") == "on",  # auto: off (TTFT, see --overlap)
                       **({"num_pages": 256} if device == "cpu" else {}))
@@ -170,6 +172,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
         "backend": "kgs", "requests": a.requests, "request_rate": a.request_rate, "input_len": a.input_len,
         "output_len": a.output_len, "max_batch": a.max_batch, "layers": a.layers,
         "chunked_prefill": getattr(a, "chunked_prefill", 0), "prefix_caching": getattr(a, "prefix_caching", False),
+        "paged_prefill": getattr(a, "paged_prefill", False),
         "shared_prefix": getattr(a, "shared_prefix", 0), "prefix_hit_tokens": int(eng.sched.prefix_hit_tokens),
         "seconds": round(dt, 3), "output_tok_per_s": round(n_out / dt, 1),
         "requests_per_s": round(len(done) / dt, 3),
@@ -250,6 +253,9 @@ def main(argv=None) -> int:
     ap.add_argument("--chunked-prefill", type=int, default=0,
                     help="> 0: mixed steps of at most this many rows (prompt chunks + decodes)")
     ap.add_argument("--prefix-caching", action="store_true", help="reuse cached pages of shared prompt prefixes")
+    ap.add_argument("--paged-prefill", action="store_true",
+                    help="mixed steps: one paged prefill-attention launch per layer for all prompt chunks "
+                         "(bf16 KV pages read in place; A/B against gather_kv + per-chunk flash attention)")
     ap.add_argument("--shared-prefix", type=int, default=0,
                     help="the first N prompt tokens are common to every request (a system prompt)")
     ap.add_argument("--request-rate", type=float, default=0.0,

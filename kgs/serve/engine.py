@@ -80,6 +80,7 @@ class EngineConfig:
     fuse_splitk: bool = True          # split-K decode partials reduced inside RoPE/KV-write and add+RMSNorm
     w4x_panels: bool = True           # tile-panel copies of the split-K decode projections (qkv, o, down)
     gate_up_panels: bool = True       # SwiGLU tile-panel copies of gate|up for the unsplit decode routes
+    paged_prefill: bool = False       # mixed steps: all prompt chunks in one attention launch over the bf16 pages
     overlap: bool = True              # plan/launch step t+1 before step t's tokens are read back (LLMEngine.step)
     seed: int = 0
 
@@ -93,9 +94,11 @@ def _bucket(n: int, cap: int) -> int:
 
 class LLMEngine:
     def __init__(self, model_cfg: LlamaConfig, cfg: EngineConfig | None = None, device="cuda", backend: str = "kgs"):
+        self.cfg = cfg = cfg or EngineConfig()
+        if cfg.paged_prefill and cfg.kv_cache_dtype == "fp8":
+            raise ValueError("paged_prefill reads bf16 KV pages: kv_cache_dtype='fp8' keeps the gather path")
         from kgs._native import _serve
 
-        self.cfg = cfg = cfg or EngineConfig()
         self.device = torch.device(device)
         self.backend = backend
         num_pages = cfg.num_pages or self._pages_from_memory(model_cfg)
@@ -104,7 +107,7 @@ class LLMEngine:
                                   decode_weights=cfg.decode_weights, kv_cache_dtype=cfg.kv_cache_dtype,
                                   packed_decode=cfg.packed_decode, prefill_weights=cfg.prefill_weights,
                                   fuse_splitk=cfg.fuse_splitk, w4x_panels=cfg.w4x_panels,
-                                  gate_up_panels=cfg.gate_up_panels)
+                                  gate_up_panels=cfg.gate_up_panels, paged_prefill=cfg.paged_prefill)
         sc = _serve.SchedulerConfig()
         sc.num_pages, sc.page_size, sc.max_batch = num_pages, PAGE, cfg.max_batch
         sc.max_prefill_tokens, sc.max_model_len, sc.pad_multiple = cfg.max_prefill_tokens, cfg.max_model_len, 128
@@ -490,7 +493,7 @@ class LLMEngine:
         return self.model.mixed(tokens if tokens is not None else self._dev(plan.tokens), self._dev(plan.positions),
                                 self._dev(plan.slots), chunks,
                                 self._dev(plan.block_tables) if nd else None,
-                                self._dev(plan.ctx_lens) if nd else None)
+                                self._dev(plan.ctx_lens) if nd else None, pf_block_tables=pf_bt)
 
     def _run_decode(self, plan, tokens: torch.Tensor | None = None) -> torch.Tensor:
         """``tokens``: the input tokens on the device (overlapped steps), else the plan's."""

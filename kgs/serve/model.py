@@ -59,7 +59,7 @@ class ServingModel:
                  num_pages: int = 1024, max_model_len: int = 8192, fused_max_batch: int = 48,
                  decode_weights: str = "bf16", kv_cache_dtype: str = "bf16", packed_decode: bool = True,
                  prefill_weights: str = "bf16", fuse_splitk: bool = True, w4x_panels: bool = True,
-                 gate_up_panels: bool = True):
+                 gate_up_panels: bool = True, paged_prefill: bool = False):
         if cfg.head_dim != D.HEAD_DIM:
             raise ValueError(f"head_dim must be {D.HEAD_DIM}")
         self.cfg, self.backend, self.device = cfg, backend, torch.device(device)
@@ -73,6 +73,11 @@ class ServingModel:
         # 256 (attention 86 -> 105 us against the 10 us rope_cache it replaces;
         # profiles/r3/decode/README.md, run r3r)
         self.rope_attn = os.environ.get("KGS_ROPE_ATTN", "0") == "1"
+        # mixed steps: every prompt chunk's attention in one launch per layer,
+        # over the KV pages in place (kgs.ops.transformer.paged_prefill_attention)
+        # instead of gather_kv + one flash-attention launch per chunk. bf16 pages
+        # on the kgs kernels only; the ref / torch backends ignore the flag
+        self.paged_prefill = paged_prefill and backend == "kgs" and kv_cache_dtype == "bf16"
         base = LlamaModel(cfg, device=device, backend="torch" if backend == "ref" else "kgs", seed=seed)
         self.oracle = base  # same weights, full-recompute forward (tests)
         self.embed, self.norm = base.embed, base.norm
@@ -368,18 +373,27 @@ class ServingModel:
 
     # ------------------------------------------------------------------ mixed
     @torch.no_grad()
-    def mixed(self, tokens, positions, slots, chunks, dec_block_tables=None, dec_ctx_lens=None) -> torch.Tensor:
+    def mixed(self, tokens, positions, slots, chunks, dec_block_tables=None, dec_ctx_lens=None,
+              pf_block_tables=None) -> torch.Tensor:
         """Chunked-prefill step: prompt chunks (rows first) plus decode rows in ONE
         pass through the projections. ``chunks``: per prefill sequence
         ``(row0, n, padded, ctx0, pages, last)`` -- rows ``row0 .. row0+padded``
         hold prompt positions ``ctx0 .. ctx0+n-1`` (then padding), ``pages`` its
         block table, ``last`` whether the chunk ends the prompt. Decode rows
         follow. Returns logits for the last row of every ``last`` chunk, then
-        for every decode row."""
+        for every decode row. ``pf_block_tables``: the chunks' ``pages`` rows as
+        one ``[nchunks, max_pages]`` tensor (the paged-prefill route; stacked from
+        ``chunks`` when absent)."""
         c = self.cfg
         hd = c.head_dim
         x = self.embed[tokens.long()].reshape(-1, c.hidden).contiguous()
         n_pf = sum(ch[2] for ch in chunks)
+        plan = None
+        if self.paged_prefill and chunks:
+            from kgs.ops.transformer import paged_prefill_attention, paged_prefill_plan
+
+            bt = pf_block_tables if pf_block_tables is not None else torch.stack([ch[4] for ch in chunks])
+            plan = paged_prefill_plan([ch[:4] for ch in chunks], bt, x.device)
         nd = x.shape[0] - n_pf
         f8 = self.prefill_f8 is not None and n_pf > 0  # W8A8 projections for the whole mixed step
         if f8:
@@ -393,6 +407,9 @@ class ServingModel:
             self._rope_cache(qkv, i, positions, slots)
             a = torch.empty((x.shape[0], c.heads * hd), dtype=torch.bfloat16, device=x.device)
             j = 0
+            if plan is not None:  # all chunks, any length and context, in one launch
+                paged_prefill_attention(qkv, self.cache.layer(i), plan, c.heads, c.kv_heads, out=a)
+                j = len(chunks)
             while j < len(chunks):
                 row0, n, p, ctx0, pages, _ = chunks[j]
                 # first chunks (no cached context) of equal padded length sit back to
