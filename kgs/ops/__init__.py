@@ -21,7 +21,8 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
 
         return getattr(gemm, name)
     if name in ("add_rmsnorm", "rms_norm", "rope_qkv_", "rope_tables", "silu_mul", "attention_qkv",
-                "add_rmsnorm_fp8", "silu_mul_fp8", "quantize_rows_fp8"):
+                "add_rmsnorm_fp8", "silu_mul_fp8", "quantize_rows_fp8", "argmax_rows", "sample_rows",
+                "sample_rows_reference"):
         from . import transformer
 
         return getattr(transformer, name)

@@ -96,6 +96,8 @@ _SIGS = {
                                   [_c_void_p, ctypes.c_float, ctypes.c_float] + [_c_void_p] * 5 + [_c_int, _c_int,
                                                                                                   _c_void_p], _c_int),
     "kgs_argmax_rows_bf16": ([_c_void_p, _c_void_p, _c_int, _c_int, _c_long, _c_void_p], _c_int),
+    # fused sampler (native/kernels/sampling.hip)
+    "kgs_sample_rows_bf16": ([_c_void_p] * 7 + [_c_int, _c_int, _c_long, _c_void_p], _c_int),
     "kgs_splitk_add_rmsnorm_bf16": ([_c_void_p, _c_int] + [_c_void_p] * 3 + [_c_int, _c_int, _c_long, _c_long,
                                                                               ctypes.c_float, _c_void_p], _c_int),
     "kgs_paged_decode_bf16": ([_c_void_p] * 8 + [_c_int] * 7 + [_c_long, _c_long, ctypes.c_float, _c_int, _c_void_p],

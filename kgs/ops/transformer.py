@@ -15,6 +15,9 @@ tests compare them with.
 * :func:`paged_prefill_plan`, :func:`paged_prefill_attention` -- every prompt
   chunk of a chunked-prefill step in one launch, keys / values read in place
   from the bf16 KV pages (``native/kernels/attention_paged.hip``)
+* :func:`sample_rows` -- temperature / top-k / top-p / seeded Gumbel-max sampling
+  of every logits row in one launch (``native/kernels/sampling.hip``), with
+  :func:`sample_rows_reference`, its float64 numpy statement
 
 Every op raises :class:`kgs.ops.NativeUnavailable` when the native library is
 missing -- there is no silent PyTorch fallback.
@@ -22,6 +25,7 @@ missing -- there is no silent PyTorch fallback.
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -92,6 +96,149 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
                                          _lib.stream_handle(x.device))
     _lib.check(rc, "argmax_rows")
     return out
+
+
+_SAMPLE_PARAMS = (("temperature", torch.float32), ("top_k", torch.int32), ("top_p", torch.float32),
+                  ("seed", torch.int64), ("counter", torch.int64))
+
+
+def sample_rows(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                seed: torch.Tensor, counter: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One token per row of bf16 GPU logits ``[rows, cols]`` (cols % 8 == 0), int64,
+    in one launch (``native/kernels/sampling.hip``). Per-row device vectors:
+    ``temperature`` fp32 (``<= 0``: greedy, :func:`argmax_rows`' answer), ``top_k``
+    int32 (on when ``0 < k < cols``; ties with the k-th largest logit are kept),
+    ``top_p`` fp32 (on when ``0 < p < 1``, applied after top-k; equal logits are kept
+    or dropped together), ``seed`` and ``counter`` int64 (the Philox4x32-10 key and
+    counter of the row's Gumbel-max draw). A row's token depends on its own logits
+    and its own five parameters only. :func:`sample_rows_reference` states the
+    semantics in numpy."""
+    # types first, then shapes, then devices: the first two are checked the same on any machine
+    vecs = (temperature, top_k, top_p, seed, counter)
+    named = list(zip(_SAMPLE_PARAMS, vecs)) + ([(("out", torch.int64), out)] if out is not None else [])
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.bfloat16:
+        raise TypeError("logits must be a bf16 tensor")
+    for (name, dtype), v in named:
+        if not isinstance(v, torch.Tensor) or v.dtype != dtype:
+            raise TypeError(f"{name} must be a {str(dtype).replace('torch.', '')} tensor")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a row-major 2-D matrix")
+    rows, cols = logits.shape
+    for (name, _), v in named:
+        if v.shape != (rows,) or not v.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous vector of length rows ({rows})")
+    _need(logits, "logits")
+    for (name, _), v in named:
+        if v.device != logits.device:
+            raise ValueError(f"{name} must be on the logits' device")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    rc = _lib.lib().kgs_sample_rows_bf16(logits.data_ptr(), out.data_ptr(), *(v.data_ptr() for v in vecs), rows, cols,
+                                         logits.stride(0), _lib.stream_handle(logits.device))
+    _lib.check(rc, "sample_rows")
+    return out
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) in exact integer arithmetic:
+    ``counter`` ``[..., 4]`` and ``key`` ``[..., 2]`` of 32-bit words (numpy,
+    broadcast against each other) -> uint32 ``[..., 4]``."""
+    import numpy as np
+
+    c = [np.asarray(counter)[..., j].astype(np.uint64) for j in range(4)]
+    k = [np.asarray(key)[..., j].astype(np.uint64) for j in range(2)]
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + np.uint64(0x9E3779B9)) & mask, (k[1] + np.uint64(0xBB67AE85)) & mask]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def sample_uniforms(seed, counter, cols: int):
+    """The sampler's uniforms, float64 ``[rows, cols]`` (exact): element i of a row
+    is ``((w >> 8) + 0.5) * 2**-24`` with w word ``i % 4`` of Philox4x32-10, key
+    ``(seed lo, seed hi)``, counter ``(i // 4, counter lo, counter hi, 0)``."""
+    import numpy as np
+
+    sd = np.asarray(seed, dtype=np.int64).astype(np.uint64)[:, None]
+    ct = np.asarray(counter, dtype=np.int64).astype(np.uint64)[:, None]
+    lo = np.uint64(0xFFFFFFFF)
+    blocks = np.arange((cols + 3) // 4, dtype=np.uint64)[None, :]
+    ctr = np.stack(np.broadcast_arrays(blocks, ct & lo, ct >> np.uint64(32), np.uint64(0)), axis=-1)
+    key = np.stack(np.broadcast_arrays(sd & lo, sd >> np.uint64(32)), axis=-1)[:, :1]
+    w = philox4x32_10(ctr, key).reshape(len(sd), -1)[:, :cols]
+    return ((w >> np.uint32(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+
+
+class SampleReference(NamedTuple):
+    tokens: "np.ndarray"    # int64 [rows]
+    kept: "np.ndarray"      # bool [rows, cols]: the set the draw is made over (greedy rows: the token alone)
+    gap: "np.ndarray"       # float64 [rows]: best minus second-best perturbed score (inf: one candidate)
+    p_margin: "np.ndarray"  # float64 [rows]: min |M(v) - top_p| over the survivors' distinct logits (inf: top-p off)
+
+
+def sample_rows_reference(logits, temperature, top_k, top_p, seed, counter) -> SampleReference:
+    """:func:`sample_rows` on the CPU in float64 (numpy): the semantics in code.
+
+    * greedy rows (``temperature <= 0``), rows holding a NaN and rows without a
+      finite maximum: the first index of the maximum, NaN counting as the maximum
+    * top-k (``0 < k < cols``): keep logits ``>=`` the k-th largest
+    * top-p (``0 < p < 1``), over the top-k survivors' softmax at temperature T:
+      with M(v) the mass of the survivors strictly above v, keep a token iff
+      M(its logit) < p
+    * token: first argmax of ``x / T - log(-log(u))`` over the kept set
+      (:func:`sample_uniforms`); ``-inf`` is never kept"""
+    import numpy as np
+
+    x = logits.detach().float().cpu().numpy().astype(np.float64) if isinstance(logits, torch.Tensor) \
+        else np.asarray(logits, dtype=np.float64)
+
+    def vec(v, dt):
+        return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(dt)
+
+    rows, cols = x.shape
+    T, k, p = vec(temperature, np.float64), vec(top_k, np.int64), vec(top_p, np.float64)
+    nan = np.isnan(x)
+    amax = np.where(nan.any(1), nan.argmax(1), np.where(nan, -np.inf, x).argmax(1)).astype(np.int64)
+    xmax = x[np.arange(rows), amax]
+    greedy = ~(T > 0) | ~np.isfinite(xmax)
+    Ts = np.where(greedy, 1.0, T)[:, None]
+    xs = np.where(greedy[:, None], 0.0, x)  # greedy rows: placeholders, overwritten below
+    srt = -np.sort(-xs, axis=1)
+    kon = (k > 0) & (k < cols)
+    thr_k = np.where(kon, srt[np.arange(rows), np.clip(k, 1, cols) - 1], -np.inf)
+    surv = (xs >= thr_k[:, None]) & (xs > -np.inf)
+    # top-p on the sorted row: exclusive cumulative mass at the first occurrence of each value
+    ssurv = (srt >= thr_k[:, None]) & (srt > -np.inf)
+    with np.errstate(over="ignore", invalid="ignore"):
+        w = np.where(ssurv, np.exp((srt - srt[:, :1]) / Ts), 0.0)
+    prob = w / w.sum(1, keepdims=True)
+    excl = np.cumsum(prob, axis=1) - prob
+    idx = np.broadcast_to(np.arange(cols), srt.shape)
+    first = np.maximum.accumulate(np.where(np.concatenate([np.ones((rows, 1), bool), srt[:, 1:] != srt[:, :-1]], 1),
+                                           idx, 0), axis=1)
+    above = np.take_along_axis(excl, first, axis=1)  # M(v) of every sorted entry
+    pon = (p > 0) & (p < 1)
+    keep_s = ssurv & (~pon[:, None] | (above < p[:, None]))
+    thr_p = np.where(keep_s, srt, np.inf).min(1)
+    kept = surv & (xs >= thr_p[:, None])
+    p_margin = np.where(pon, np.where(ssurv, np.abs(above - p[:, None]), np.inf).min(1), np.inf)
+    u = sample_uniforms(vec(seed, np.int64), vec(counter, np.int64), cols)
+    score = np.where(kept, xs / Ts - np.log(-np.log(u)), -np.inf)
+    tokens = score.argmax(1).astype(np.int64)
+    if cols > 1:
+        top2 = -np.partition(-score, 1, axis=1)[:, :2]
+        with np.errstate(invalid="ignore"):
+            gap = top2[:, 0] - top2[:, 1]
+    else:
+        gap = np.full(rows, np.inf)
+    tokens = np.where(greedy, amax, tokens)
+    onehot = np.arange(cols)[None, :] == amax[:, None]
+    kept = np.where(greedy[:, None], onehot, kept)
+    gap = np.where(greedy, np.inf, gap)
+    p_margin = np.where(greedy, np.inf, p_margin)
+    return SampleReference(tokens, kept, gap, p_margin)
 
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:

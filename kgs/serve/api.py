@@ -387,6 +387,9 @@ def main(argv=None) -> int:
     ap.add_argument("--paged-prefill", action="store_true",
                     help="mixed steps: one paged prefill-attention launch per layer for all prompt chunks, reading "
                          "the bf16 KV pages in place (no gather); not with --kv-cache-dtype fp8")
+    ap.add_argument("--device-sampler", action="store_true",
+                    help="sample every step in one native launch (temperature, top-k, top-p, seeds); seeded requests "
+                         "then keep overlapped steps. Same distribution as the default route, other random streams")
     ap.add_argument("--overlap", action=argparse.BooleanOptionalAction, default=False,
                     help="overlapped engine steps: ~7 %% lower TPOT for a few ms more TTFT (a request arriving "
                          "while a step is in flight misses that step; profiles/r5/overlap/README.md)")
@@ -411,7 +414,8 @@ def main(argv=None) -> int:
     ec = EngineConfig(max_batch=a.max_batch, max_model_len=a.max_model_len, cuda_graphs=not a.no_graphs,
                       chunked_prefill=a.chunked_prefill, prefix_caching=a.prefix_caching,
                       kv_cache_dtype=a.kv_cache_dtype, decode_weights=a.decode_weights,
-                      prefill_weights=a.prefill_weights, overlap=a.overlap, paged_prefill=a.paged_prefill)
+                      prefill_weights=a.prefill_weights, overlap=a.overlap, paged_prefill=a.paged_prefill,
+                      device_sampler=a.device_sampler)
     if a.data_parallel > 1 or a.engine_process:
         import dataclasses
 

@@ -49,7 +49,7 @@ def run_engine(a) -> dict:
                       packed_decode=not a.no_packed_decode, prefill_weights=a.prefill_weights,
                       fuse_splitk=not a.no_fuse_splitk, w4x_panels=not a.no_w4x_panels,
                       gate_up_panels=not a.no_gate_up_panels, overlap=a.overlap != "off",
-                      paged_prefill=a.paged_prefill)
+                      paged_prefill=a.paged_prefill, device_sampler=a.device_sampler)
     t0 = time.perf_counter()
     eng = LLMEngine(mc, ec, device="cuda", backend="kgs")
     t_load = time.perf_counter() - t0
@@ -61,7 +61,7 @@ def run_engine(a) -> dict:
     torch.cuda.synchronize()
     t_warm = time.perf_counter() - t0
     prompts = _prompts(a.requests, a.input_len, mc.vocab, shared=a.shared_prefix)
-    params = SamplingParams(max_tokens=a.output_len, ignore_eos=True)
+    params = _sampling(a, a.requests)
     if a.gc_freeze:
         import gc
 
@@ -95,6 +95,8 @@ def run_engine(a) -> dict:
         "gate_up_panels": eng.model.gate_up_panels is not None, "overlap": eng.overlap,
         "nt_weights": NT_WEIGHTS,
         "chunked_prefill": a.chunked_prefill, "paged_prefill": a.paged_prefill,
+        "device_sampler": eng.device_sampler, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
+        "seeded": a.seeded,
         "prefix_caching": a.prefix_caching, "shared_prefix": a.shared_prefix,
         "prefix_hit_tokens": int(eng.sched.prefix_hit_tokens),
         "seconds": round(dt, 3), "output_tok_per_s": round(n_out / dt, 1),
@@ -103,6 +105,18 @@ def run_engine(a) -> dict:
         "load_s": round(t_load, 1), "warmup_s": round(t_warm, 1), "stats": dict(eng.stats),
         "tile_queue_dirty_slots": tq["dirty_slots"],
     }
+
+
+def _sampling(a, n: int) -> list:
+    """The n requests' SamplingParams from --temperature / --top-k / --top-p
+    (greedy by default) and --seeded (request i gets seed i)."""
+    from .engine import SamplingParams
+
+    kw = dict(max_tokens=a.output_len, ignore_eos=True, temperature=getattr(a, "temperature", 0.0),
+              top_k=getattr(a, "top_k", 0), top_p=getattr(a, "top_p", 1.0))
+    if getattr(a, "seeded", False):
+        return [SamplingParams(seed=i, **kw) for i in range(n)]
+    return [SamplingParams(**kw)] * n
 
 
 def _pct(v, q):
@@ -131,6 +145,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
                       paged_prefill=getattr(a, "paged_prefill", False),
                       packed_decode=not getattr(a, "no_packed_decode", False),
                       overlap=getattr(a, "overlap", "auto") == "on",  # auto: off (TTFT, see --overlap)
+                      device_sampler=getattr(a, "device_sampler", False),
                       **({"num_pages": 256} if device == "cpu" else {}))
     eng = LLMEngine(mc, ec, device=device, backend=backend)
     if not a.no_graphs:
@@ -141,7 +156,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
     rng = np.random.default_rng(1)
     arrivals = np.cumsum(rng.exponential(1.0 / a.request_rate, size=a.requests))
     prompts = _prompts(a.requests, a.input_len, mc.vocab, shared=getattr(a, "shared_prefix", 0))
-    params = SamplingParams(max_tokens=a.output_len, ignore_eos=True)
+    params = _sampling(a, a.requests)
     tok_times: dict = {}
     done = []
     t0 = time.perf_counter()
@@ -149,7 +164,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
     while i < a.requests or eng.has_work():
         now = time.perf_counter() - t0
         while i < a.requests and arrivals[i] <= now:
-            rid = eng.add_request(prompts[i], params)
+            rid = eng.add_request(prompts[i], params[i])
             eng.requests[rid].t_arrival = t0 + arrivals[i]
             tok_times[rid] = []
             i += 1
@@ -173,6 +188,8 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
         "output_len": a.output_len, "max_batch": a.max_batch, "layers": a.layers,
         "chunked_prefill": getattr(a, "chunked_prefill", 0), "prefix_caching": getattr(a, "prefix_caching", False),
         "paged_prefill": getattr(a, "paged_prefill", False),
+        "device_sampler": eng.device_sampler, "temperature": getattr(a, "temperature", 0.0),
+        "top_k": getattr(a, "top_k", 0), "top_p": getattr(a, "top_p", 1.0), "seeded": getattr(a, "seeded", False),
         "shared_prefix": getattr(a, "shared_prefix", 0), "prefix_hit_tokens": int(eng.sched.prefix_hit_tokens),
         "seconds": round(dt, 3), "output_tok_per_s": round(n_out / dt, 1),
         "requests_per_s": round(len(done) / dt, 3),
@@ -256,6 +273,14 @@ def main(argv=None) -> int:
     ap.add_argument("--paged-prefill", action="store_true",
                     help="mixed steps: one paged prefill-attention launch per layer for all prompt chunks "
                          "(bf16 KV pages read in place; A/B against gather_kv + per-chunk flash attention)")
+    ap.add_argument("--device-sampler", action="store_true",
+                    help="sample every step in one native launch (EngineConfig.device_sampler; A/B against the torch "
+                         "sampling chain, which only sampled traffic takes: see --temperature)")
+    ap.add_argument("--temperature", type=float, default=0.0, help="every request's temperature (0 = greedy)")
+    ap.add_argument("--top-k", type=int, default=0, help="every request's top-k (0 = off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="every request's top-p (1 = off)")
+    ap.add_argument("--seeded", action="store_true",
+                    help="request i carries seed i (without --device-sampler seeded requests run one step at a time)")
     ap.add_argument("--shared-prefix", type=int, default=0,
                     help="the first N prompt tokens are common to every request (a system prompt)")
     ap.add_argument("--request-rate", type=float, default=0.0,

@@ -59,6 +59,8 @@ class Request:
     # from the model's distribution before temperature / top-k / top-p
     logprobs: list = field(default_factory=list)
     gen: object = None  # torch.Generator of a seeded request
+    sampled: int = 0    # tokens sampled so far: the device sampler's Philox counter (carries on across preemption)
+    draw: tuple | None = None  # device sampler: (temperature, top_k, top_p, seed), fixed at add_request
 
 
 @dataclass
@@ -82,7 +84,24 @@ class EngineConfig:
     gate_up_panels: bool = True       # SwiGLU tile-panel copies of gate|up for the unsplit decode routes
     paged_prefill: bool = False       # mixed steps: all prompt chunks in one attention launch over the bf16 pages
     overlap: bool = True              # plan/launch step t+1 before step t's tokens are read back (LLMEngine.step)
+    device_sampler: bool = False      # temperature / top-k / top-p / seeds: one sample_rows launch per step (kgs, GPU)
     seed: int = 0
+
+
+def _mix64(seed: int, rid: int) -> int:
+    """The sampling seed of a request that gave none: splitmix64's finaliser over
+    the engine seed and the request id."""
+    m = (1 << 64) - 1
+    z = (seed * 0x9E3779B97F4A7C15 + rid + 1) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def _i64(v: int) -> int:
+    """The low 64 bits of v as a signed integer (an int64 array element)."""
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
 
 
 def _bucket(n: int, cap: int) -> int:
@@ -147,6 +166,9 @@ class LLMEngine:
         self._phases = [] if os.environ.get("KGS_HOST_PHASES", "0") == "1" else None
         self._pinned = None  # two host buffers the in-flight tokens are copied into, alternately
         self._flip = 0
+        # EngineConfig.device_sampler: like paged_prefill, only the kgs backend on a GPU has the kernel
+        self.device_sampler = cfg.device_sampler and backend == "kgs" and self.device.type == "cuda"
+        self._draw = None  # the sampler's per-row parameters: two packed pinned host buffers + one on the device
 
     def _pages_from_memory(self, mc: LlamaConfig) -> int:
         if self.device.type != "cuda":
@@ -175,6 +197,10 @@ class LLMEngine:
             raise ValueError(f"request does not fit: prompt {len(prompt)} + max_tokens {params.max_tokens} "
                              f"(max_model_len {self.cfg.max_model_len}, {self.num_pages} pages)")
         self.requests[rid] = Request(rid, list(prompt), params, t_arrival=time.perf_counter())
+        if self.device_sampler:
+            seed = params.seed if params.seed is not None else _mix64(self.cfg.seed, rid)
+            self.requests[rid].draw = (float(params.temperature), min(max(int(params.top_k), 0), 2**31 - 1),
+                                       float(params.top_p), _i64(int(seed)))
         # requests that need per-row work after the model step (the common greedy /
         # plain-sampling batch skips those scans entirely)
         if params.logprobs is not None:
@@ -205,8 +231,11 @@ class LLMEngine:
         """Whether the next step may be planned before the current one's tokens
         are known: logprobs, penalties and seeded sampling read per-step host
         state (the output so far, per-request generators), so a batch holding
-        any of them runs one step at a time."""
-        return self.overlap and not (self._want_lp or self._want_pen or self._seeded)
+        any of them runs one step at a time. The device sampler draws a seeded
+        row from (seed, tokens sampled so far), both known ahead of the tokens:
+        with it seeded requests overlap like any other."""
+        seeded = self._seeded and not self.device_sampler
+        return self.overlap and not (self._want_lp or self._want_pen or seeded)
 
     def step(self) -> list[tuple[int, int, bool]]:
         """Run one scheduler step; returns [(request id, new token, finished)].
@@ -606,29 +635,93 @@ class LLMEngine:
             out[j] = (chosen[n], list(zip(top_i[n][:kj], top_v[n][:kj])))
         return out
 
-    def _penalize(self, ids, logits: torch.Tensor) -> torch.Tensor:
-        """Presence / frequency / repetition penalties on the rows that ask for
-        them (a per-row token-count vector built from that request's tokens)."""
+    def _penalized_rows(self, ids, logits: torch.Tensor):
+        """(rows, their logits in fp32 after the penalties) for the rows whose
+        request asks for presence / frequency / repetition penalties (a per-row
+        token-count vector built from that request's tokens); ([], None) when
+        none does."""
         if not self._want_pen:
-            return logits
+            return [], None
         rows = [j for j, r in enumerate(ids) if int(r) in self._want_pen]
         if not rows:
-            return logits
-        logits = logits.float().clone()
-        vocab = logits.shape[1]
-        for j in rows:
+            return [], None
+        sub = logits[rows].float()
+        vocab = sub.shape[1]
+        for n, j in enumerate(rows):
             r = self.requests[int(ids[j])]
             p = r.params
             if r.output and (p.presence_penalty or p.frequency_penalty):
                 cnt = torch.bincount(torch.as_tensor(r.output, device=logits.device), minlength=vocab)[:vocab]
-                logits[j] -= p.frequency_penalty * cnt + p.presence_penalty * (cnt > 0)
+                sub[n] -= p.frequency_penalty * cnt + p.presence_penalty * (cnt > 0)
             if p.repetition_penalty != 1.0:
                 seen = torch.as_tensor(sorted(set(r.prompt) | set(r.output)), device=logits.device)
-                v = logits[j, seen]
-                logits[j, seen] = torch.where(v > 0, v / p.repetition_penalty, v * p.repetition_penalty)
+                v = sub[n, seen]
+                sub[n, seen] = torch.where(v > 0, v / p.repetition_penalty, v * p.repetition_penalty)
+        return rows, sub
+
+    def _penalize(self, ids, logits: torch.Tensor) -> torch.Tensor:
+        """The step's logits in fp32 with the penalties applied (the logits
+        themselves when no row asks for any)."""
+        rows, sub = self._penalized_rows(ids, logits)
+        if not rows:
+            return logits
+        logits = logits.float().clone()
+        logits[rows] = sub
         return logits
 
+    def _sample_device(self, ids, logits: torch.Tensor) -> torch.Tensor:
+        """EngineConfig.device_sampler: the whole step's tokens from one
+        sample_rows launch, greedy rows included. The per-row parameters go
+        through one packed pinned buffer and one async copy; there are two such
+        buffers, used alternately, because an overlapped step fills the next
+        one while this one's copy may still be queued. Row j draws with
+        (its request's seed, the number of tokens that request has sampled):
+        neither depends on its batch mates or on a token not yet read back.
+        Penalised rows are computed in fp32 as on the torch route and rounded
+        back to bf16 (one extra rounding of those rows' logits); every row then
+        takes the kernel."""
+        from kgs.ops.transformer import sample_rows
+
+        if not (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2):
+            raise RuntimeError(f"device_sampler needs bf16 GPU logits [rows, vocab], got {logits.dtype} "
+                               f"{tuple(logits.shape)} on {logits.device}")
+        rows, sub = self._penalized_rows(ids, logits)
+        if rows:
+            logits = logits.clone()
+            logits[rows] = sub.to(torch.bfloat16)
+        n, mb = len(ids), self.cfg.max_batch
+        if self._draw is None:
+            # per buffer: seed i64[mb] | counter i64[mb] | temperature f32[mb] | top_k i32[mb] | top_p f32[mb]
+            offs = {"seed": (0, np.int64), "counter": (8 * mb, np.int64), "temperature": (16 * mb, np.float32),
+                    "top_k": (20 * mb, np.int32), "top_p": (24 * mb, np.float32)}
+            host = [torch.zeros(28 * mb, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            dev = torch.zeros(28 * mb, dtype=torch.uint8, device=self.device)
+            tdt = {np.int64: torch.int64, np.float32: torch.float32, np.int32: torch.int32}
+            self._draw = {
+                "host": host, "dev": dev, "flip": 0,
+                "np": [{k: h.numpy()[o:o + mb * np.dtype(dt).itemsize].view(dt) for k, (o, dt) in offs.items()}
+                       for h in host],
+                "views": {k: dev[o:o + mb * np.dtype(dt).itemsize].view(tdt[dt]) for k, (o, dt) in offs.items()}}
+        d = self._draw
+        hn = d["np"][d["flip"]]
+        reqs = [self.requests[int(r)] for r in ids]
+        draws = [r.draw for r in reqs]
+        hn["temperature"][:n] = [w[0] for w in draws]
+        hn["top_k"][:n] = [w[1] for w in draws]
+        hn["top_p"][:n] = [w[2] for w in draws]
+        hn["seed"][:n] = [w[3] for w in draws]
+        hn["counter"][:n] = [r.sampled for r in reqs]
+        for r in reqs:
+            r.sampled += 1
+        d["dev"].copy_(d["host"][d["flip"]], non_blocking=True)
+        d["flip"] ^= 1
+        v = d["views"]
+        return sample_rows(logits, v["temperature"][:n], v["top_k"][:n], v["top_p"][:n], v["seed"][:n],
+                           v["counter"][:n])
+
     def _sample(self, ids, logits: torch.Tensor) -> torch.Tensor:
+        if self.device_sampler:
+            return self._sample_device(ids, logits)
         logits = self._penalize(ids, logits)
         ps = [self.requests[int(r)].params for r in ids]
         if all(p.temperature <= 0 for p in ps):
