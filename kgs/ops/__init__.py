@@ -22,7 +22,8 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         return getattr(gemm, name)
     if name in ("add_rmsnorm", "rms_norm", "rope_qkv_", "rope_tables", "silu_mul", "attention_qkv",
                 "add_rmsnorm_fp8", "silu_mul_fp8", "quantize_rows_fp8", "argmax_rows", "sample_rows",
-                "sample_rows_reference"):
+                "sample_rows_reference", "penalize_rows", "token_counts_add", "logprob_rows",
+                "penalize_rows_reference", "logprob_rows_reference"):
         from . import transformer
 
         return getattr(transformer, name)

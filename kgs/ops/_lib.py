@@ -98,6 +98,10 @@ _SIGS = {
     "kgs_argmax_rows_bf16": ([_c_void_p, _c_void_p, _c_int, _c_int, _c_long, _c_void_p], _c_int),
     # fused sampler (native/kernels/sampling.hip)
     "kgs_sample_rows_bf16": ([_c_void_p] * 7 + [_c_int, _c_int, _c_long, _c_void_p], _c_int),
+    # device penalties and logprobs (native/kernels/logit_ops.hip)
+    "kgs_penalize_rows_bf16": ([_c_void_p] * 7 + [_c_int, _c_int, _c_long, _c_int, _c_void_p], _c_int),
+    "kgs_token_counts_add": ([_c_void_p] * 3 + [_c_int, _c_int, _c_int, _c_void_p], _c_int),
+    "kgs_logprob_rows_bf16": ([_c_void_p] * 6 + [_c_int, _c_int, _c_long, _c_void_p], _c_int),
     "kgs_splitk_add_rmsnorm_bf16": ([_c_void_p, _c_int] + [_c_void_p] * 3 + [_c_int, _c_int, _c_long, _c_long,
                                                                               ctypes.c_float, _c_void_p], _c_int),
     "kgs_paged_decode_bf16": ([_c_void_p] * 8 + [_c_int] * 7 + [_c_long, _c_long, ctypes.c_float, _c_int, _c_void_p],

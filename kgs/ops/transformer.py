@@ -18,6 +18,10 @@ tests compare them with.
 * :func:`sample_rows` -- temperature / top-k / top-p / seeded Gumbel-max sampling
   of every logits row in one launch (``native/kernels/sampling.hip``), with
   :func:`sample_rows_reference`, its float64 numpy statement
+* :func:`penalize_rows`, :func:`token_counts_add`, :func:`logprob_rows` -- penalties
+  from a device token-count table and logprobs of the sampled token and the top k
+  (``native/kernels/logit_ops.hip``), with :func:`penalize_rows_reference` (float32,
+  bit for bit) and :func:`logprob_rows_reference` (float64)
 
 Every op raises :class:`kgs.ops.NativeUnavailable` when the native library is
 missing -- there is no silent PyTorch fallback.
@@ -239,6 +243,219 @@ def sample_rows_reference(logits, temperature, top_k, top_p, seed, counter) -> S
     gap = np.where(greedy, np.inf, gap)
     p_margin = np.where(greedy, np.inf, p_margin)
     return SampleReference(tokens, kept, gap, p_margin)
+
+
+LOGPROB_KMAX = 32            # logprob_rows: the most top entries a row can ask for
+COUNT_PROMPT = 1 << 30       # count word: the token occurs in the request's prompt
+COUNT_MASK = COUNT_PROMPT - 1  # count word: the token's count in the request's output
+
+
+def _typed(named) -> None:
+    for name, dtype, v in named:
+        if not isinstance(v, torch.Tensor) or v.dtype != dtype:
+            raise TypeError(f"{name} must be a {str(dtype).replace('torch.', '')} tensor")
+
+
+def _row_vectors(named, rows: int) -> None:
+    for name, _, v in named:
+        if v.shape != (rows,) or not v.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous vector of length rows ({rows})")
+
+
+def _same_device(named, ref: torch.Tensor, what: str) -> None:
+    for name, _, v in named:
+        if v.device != ref.device:
+            raise ValueError(f"{name} must be on the {what}' device")
+
+
+def penalize_rows(logits: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor, rep: torch.Tensor,
+                  slot: torch.Tensor, counts: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The penalised copy of bf16 GPU logits ``[rows, cols]`` (cols % 8 == 0) in one
+    launch (``native/kernels/logit_ops.hip``): contiguous bf16 ``[rows, cols]``.
+    Per-row device vectors ``freq``, ``pres``, ``rep`` (fp32) and ``slot`` (int32): row
+    j reads the count words ``counts[slot[j]]`` of the int32 table ``[slots, cols]``
+    (``w & COUNT_MASK``: the token's count n in the output, ``w & COUNT_PROMPT``: a
+    prompt token). Rows with a slot outside ``[0, slots)`` and elements with ``w == 0``
+    are copied bit for bit. Otherwise, in fp32 and each step rounded once:
+    ``v -= freq * n + pres`` when ``n > 0``, then ``v = v / rep if v > 0 else v * rep``
+    when ``rep != 1``, then bf16 nearest-even (a NaN comes out as 0x7fc0).
+    :func:`penalize_rows_reference` is the same in numpy, bit for bit."""
+    vecs = [("freq", torch.float32, freq), ("pres", torch.float32, pres), ("rep", torch.float32, rep),
+            ("slot", torch.int32, slot)]
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.bfloat16:
+        raise TypeError("logits must be a bf16 tensor")
+    _typed(vecs + [("counts", torch.int32, counts)] + ([("out", torch.bfloat16, out)] if out is not None else []))
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a row-major 2-D matrix")
+    rows, cols = logits.shape
+    _row_vectors(vecs, rows)
+    if counts.dim() != 2 or counts.shape[1] != cols or not counts.is_contiguous():
+        raise ValueError(f"counts must be a contiguous [slots, cols ({cols})] table")
+    if out is not None and (tuple(out.shape) != (rows, cols) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous [rows ({rows}), cols ({cols})] matrix")
+    _need(logits, "logits")
+    _same_device(vecs + [("counts", None, counts)] + ([("out", None, out)] if out is not None else []), logits,
+                 "logits")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.bfloat16, device=logits.device)
+    rc = _lib.lib().kgs_penalize_rows_bf16(logits.data_ptr(), out.data_ptr(), freq.data_ptr(), pres.data_ptr(),
+                                           rep.data_ptr(), slot.data_ptr(), counts.data_ptr(), rows, cols,
+                                           logits.stride(0), counts.shape[0], _lib.stream_handle(logits.device))
+    _lib.check(rc, "penalize_rows")
+    return out
+
+
+def token_counts_add(counts: torch.Tensor, tok: torch.Tensor, slot: torch.Tensor) -> torch.Tensor:
+    """``counts[slot[j], tok[j]] += 1`` for every j with ``0 <= slot[j] < slots`` and
+    ``0 <= tok[j] < cols``, in place and in one launch; other rows write nothing.
+    ``counts``: int32 GPU table ``[slots, cols]``; ``tok``: int64 ``[rows]`` (the
+    sampler's output); ``slot``: int32 ``[rows]``. The slots ``>= 0`` of one call must
+    be distinct: the update is not atomic."""
+    vecs = [("tok", torch.int64, tok), ("slot", torch.int32, slot)]
+    _typed([("counts", torch.int32, counts)] + vecs)
+    if counts.dim() != 2 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous [slots, cols] table")
+    if tok.dim() != 1:
+        raise ValueError("tok must be a vector")
+    _row_vectors(vecs, tok.shape[0])
+    if not counts.is_cuda:
+        raise ValueError("counts must be on a GPU")
+    _same_device(vecs, counts, "counts")
+    rc = _lib.lib().kgs_token_counts_add(counts.data_ptr(), tok.data_ptr(), slot.data_ptr(), tok.shape[0],
+                                         counts.shape[0], counts.shape[1], _lib.stream_handle(counts.device))
+    _lib.check(rc, "token_counts_add")
+    return counts
+
+
+def logprob_rows(logits: torch.Tensor, tok: torch.Tensor, want: torch.Tensor, lp: torch.Tensor | None = None,
+                 top_val: torch.Tensor | None = None, top_idx: torch.Tensor | None = None):
+    """Logprobs of bf16 GPU logits ``[rows, cols]`` (cols % 8 == 0) in one launch:
+    ``(lp, top_val, top_idx)``, fp32 ``[rows]``, fp32 ``[rows, 32]``, int32 ``[rows, 32]``.
+    ``tok`` int64 ``[rows]``: the token whose logprob goes to ``lp`` (NaN outside
+    ``[0, cols)``); ``want`` int32 ``[rows]``: ``< 0`` skips the row, else its
+    ``k = min(want, cols, 32)`` most likely tokens, by logit descending then index
+    ascending (-0 equals +0), go to ``top_idx[:k]`` with their logprobs in ``top_val[:k]``.
+    Entries past k and skipped rows are left as they were (NaN / -1 in buffers made
+    here). A logprob is ``(x_i - m) - log(sum_j exp(x_j - m))`` in fp32, m the row
+    maximum; a row with a NaN or without a finite maximum gives NaN and indices
+    ``0..k-1``. :func:`logprob_rows_reference` states the same in float64."""
+    vecs = [("tok", torch.int64, tok), ("want", torch.int32, want)]
+    outs = [(n, d, v) for n, d, v in (("lp", torch.float32, lp), ("top_val", torch.float32, top_val),
+                                      ("top_idx", torch.int32, top_idx)) if v is not None]
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.bfloat16:
+        raise TypeError("logits must be a bf16 tensor")
+    _typed(vecs + outs)
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be a row-major 2-D matrix")
+    rows, cols = logits.shape
+    _row_vectors(vecs + outs[:1 if lp is not None else 0], rows)
+    for name, _, v in outs:
+        if name != "lp" and (tuple(v.shape) != (rows, LOGPROB_KMAX) or not v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous [rows ({rows}), {LOGPROB_KMAX}] matrix")
+    _need(logits, "logits")
+    _same_device(vecs + outs, logits, "logits")
+    dev = logits.device
+    if lp is None:
+        lp = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev)
+    if top_val is None:
+        top_val = torch.full((rows, LOGPROB_KMAX), float("nan"), dtype=torch.float32, device=dev)
+    if top_idx is None:
+        top_idx = torch.full((rows, LOGPROB_KMAX), -1, dtype=torch.int32, device=dev)
+    rc = _lib.lib().kgs_logprob_rows_bf16(logits.data_ptr(), tok.data_ptr(), want.data_ptr(), lp.data_ptr(),
+                                          top_val.data_ptr(), top_idx.data_ptr(), rows, cols, logits.stride(0),
+                                          _lib.stream_handle(dev))
+    _lib.check(rc, "logprob_rows")
+    return lp, top_val, top_idx
+
+
+def _np(v, dt):
+    import numpy as np
+
+    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(dt)
+
+
+def bf16_bits(x):
+    """bf16 bit patterns (numpy uint16) of a bf16 tensor, of an array of bit patterns
+    (uint16, taken as they are) or of floats (rounded to bf16, nearest-even; a NaN
+    becomes 0x7fc0)."""
+    import numpy as np
+
+    if isinstance(x, torch.Tensor):
+        if x.dtype == torch.bfloat16:
+            return x.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16).copy()
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.dtype == np.uint16:
+        return x.copy()
+    f = np.ascontiguousarray(x, dtype=np.float32)
+    u = f.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    return np.where(np.isnan(f), np.uint16(0x7FC0), r)
+
+
+def bf16_bits_to_float(bits):
+    """float32 values of bf16 bit patterns (numpy uint16)."""
+    import numpy as np
+
+    return (np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def penalize_rows_reference(logits, freq, pres, rep, slot, counts):
+    """:func:`penalize_rows` on the CPU in float32 numpy, one rounding per step:
+    the bf16 bit patterns (uint16 ``[rows, cols]``) the kernel must produce.
+    ``logits``: a bf16 tensor, uint16 bit patterns or floats (:func:`bf16_bits`)."""
+    import numpy as np
+
+    h = bf16_bits(logits)
+    rows, cols = h.shape
+    f, p, r = _np(freq, np.float32), _np(pres, np.float32), _np(rep, np.float32)
+    sl, tab = _np(slot, np.int64), _np(counts, np.int64).reshape(-1, cols)
+    out = h.copy()
+    with np.errstate(all="ignore"):
+        for j in range(rows):
+            if not 0 <= sl[j] < len(tab):
+                continue
+            w = tab[sl[j]]
+            n = w & COUNT_MASK
+            v = bf16_bits_to_float(h[j])
+            a = f[j] * n.astype(np.float32)
+            t = a + p[j]
+            v = np.where(n > 0, v - t, v).astype(np.float32)
+            if r[j] != np.float32(1):
+                v = np.where(v > 0, v / r[j], v * r[j]).astype(np.float32)
+            out[j] = np.where(w != 0, bf16_bits(v), h[j])
+    return out
+
+
+def logprob_rows_reference(logits, tok, want):
+    """:func:`logprob_rows` on the CPU in float64 numpy: ``(lp [rows], top_val
+    [rows, 32], top_idx [rows, 32])`` (float64, float64, int64); skipped rows and
+    entries past k hold NaN / -1."""
+    import numpy as np
+
+    x = bf16_bits_to_float(logits).astype(np.float64) if getattr(logits, "dtype", None) == np.uint16 else \
+        (logits.detach().float().cpu().numpy().astype(np.float64) if isinstance(logits, torch.Tensor)
+         else np.asarray(logits, dtype=np.float64))
+    rows, cols = x.shape
+    tk, wk = _np(tok, np.int64), _np(want, np.int64)
+    lp = np.full(rows, np.nan)
+    tv = np.full((rows, LOGPROB_KMAX), np.nan)
+    ti = np.full((rows, LOGPROB_KMAX), -1, dtype=np.int64)
+    for j in range(rows):
+        if wk[j] < 0:
+            continue
+        k = int(min(wk[j], cols, LOGPROB_KMAX))
+        m = np.nan if np.isnan(x[j]).any() else x[j].max()
+        if not np.isfinite(m):
+            ti[j, :k] = np.arange(k)
+            continue
+        with np.errstate(divide="ignore"):
+            lps = (x[j] - m) - np.log(np.exp(x[j] - m).sum())
+        if 0 <= tk[j] < cols:
+            lp[j] = lps[tk[j]]
+        order = np.lexsort((np.arange(cols), -x[j]))[:k]  # logit descending, then index ascending (-0 == +0)
+        ti[j, :k], tv[j, :k] = order, lps[order]
+    return lp, tv, ti
 
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:

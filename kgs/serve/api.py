@@ -390,6 +390,9 @@ def main(argv=None) -> int:
     ap.add_argument("--device-sampler", action="store_true",
                     help="sample every step in one native launch (temperature, top-k, top-p, seeds); seeded requests "
                          "then keep overlapped steps. Same distribution as the default route, other random streams")
+    ap.add_argument("--device-logit-ops", action="store_true",
+                    help="with --device-sampler: penalties from a device token-count table and logprobs (k <= 32) in "
+                         "the step's own launches; such requests then keep overlapped steps (docs/serving.md)")
     ap.add_argument("--overlap", action=argparse.BooleanOptionalAction, default=False,
                     help="overlapped engine steps: ~7 %% lower TPOT for a few ms more TTFT (a request arriving "
                          "while a step is in flight misses that step; profiles/r5/overlap/README.md)")
@@ -415,7 +418,7 @@ def main(argv=None) -> int:
                       chunked_prefill=a.chunked_prefill, prefix_caching=a.prefix_caching,
                       kv_cache_dtype=a.kv_cache_dtype, decode_weights=a.decode_weights,
                       prefill_weights=a.prefill_weights, overlap=a.overlap, paged_prefill=a.paged_prefill,
-                      device_sampler=a.device_sampler)
+                      device_sampler=a.device_sampler, device_logit_ops=a.device_logit_ops)
     if a.data_parallel > 1 or a.engine_process:
         import dataclasses
 

@@ -49,7 +49,8 @@ def run_engine(a) -> dict:
                       packed_decode=not a.no_packed_decode, prefill_weights=a.prefill_weights,
                       fuse_splitk=not a.no_fuse_splitk, w4x_panels=not a.no_w4x_panels,
                       gate_up_panels=not a.no_gate_up_panels, overlap=a.overlap != "off",
-                      paged_prefill=a.paged_prefill, device_sampler=a.device_sampler)
+                      paged_prefill=a.paged_prefill, device_sampler=a.device_sampler,
+                      device_logit_ops=getattr(a, "device_logit_ops", False))
     t0 = time.perf_counter()
     eng = LLMEngine(mc, ec, device="cuda", backend="kgs")
     t_load = time.perf_counter() - t0
@@ -96,7 +97,7 @@ def run_engine(a) -> dict:
         "nt_weights": NT_WEIGHTS,
         "chunked_prefill": a.chunked_prefill, "paged_prefill": a.paged_prefill,
         "device_sampler": eng.device_sampler, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
-        "seeded": a.seeded,
+        "seeded": a.seeded, **_logit_ops_record(a, eng),
         "prefix_caching": a.prefix_caching, "shared_prefix": a.shared_prefix,
         "prefix_hit_tokens": int(eng.sched.prefix_hit_tokens),
         "seconds": round(dt, 3), "output_tok_per_s": round(n_out / dt, 1),
@@ -113,10 +114,21 @@ def _sampling(a, n: int) -> list:
     from .engine import SamplingParams
 
     kw = dict(max_tokens=a.output_len, ignore_eos=True, temperature=getattr(a, "temperature", 0.0),
-              top_k=getattr(a, "top_k", 0), top_p=getattr(a, "top_p", 1.0))
+              top_k=getattr(a, "top_k", 0), top_p=getattr(a, "top_p", 1.0), logprobs=getattr(a, "logprobs", None),
+              presence_penalty=getattr(a, "presence_penalty", 0.0),
+              frequency_penalty=getattr(a, "frequency_penalty", 0.0),
+              repetition_penalty=getattr(a, "repetition_penalty", 1.0))
     if getattr(a, "seeded", False):
         return [SamplingParams(seed=i, **kw) for i in range(n)]
     return [SamplingParams(**kw)] * n
+
+
+def _logit_ops_record(a, eng) -> dict:
+    """The record's echo of --device-logit-ops, --logprobs and the penalty flags."""
+    return {"device_logit_ops": eng.device_logit_ops, "logprobs": getattr(a, "logprobs", None),
+            "presence_penalty": getattr(a, "presence_penalty", 0.0),
+            "frequency_penalty": getattr(a, "frequency_penalty", 0.0),
+            "repetition_penalty": getattr(a, "repetition_penalty", 1.0)}
 
 
 def _pct(v, q):
@@ -146,6 +158,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
                       packed_decode=not getattr(a, "no_packed_decode", False),
                       overlap=getattr(a, "overlap", "auto") == "on",  # auto: off (TTFT, see --overlap)
                       device_sampler=getattr(a, "device_sampler", False),
+                      device_logit_ops=getattr(a, "device_logit_ops", False),
                       **({"num_pages": 256} if device == "cpu" else {}))
     eng = LLMEngine(mc, ec, device=device, backend=backend)
     if not a.no_graphs:
@@ -190,6 +203,7 @@ def run_online(a, mc=None, device="cuda", backend="kgs") -> dict:
         "paged_prefill": getattr(a, "paged_prefill", False),
         "device_sampler": eng.device_sampler, "temperature": getattr(a, "temperature", 0.0),
         "top_k": getattr(a, "top_k", 0), "top_p": getattr(a, "top_p", 1.0), "seeded": getattr(a, "seeded", False),
+        **_logit_ops_record(a, eng),
         "shared_prefix": getattr(a, "shared_prefix", 0), "prefix_hit_tokens": int(eng.sched.prefix_hit_tokens),
         "seconds": round(dt, 3), "output_tok_per_s": round(n_out / dt, 1),
         "requests_per_s": round(len(done) / dt, 3),
@@ -281,6 +295,14 @@ def main(argv=None) -> int:
     ap.add_argument("--top-p", type=float, default=1.0, help="every request's top-p (1 = off)")
     ap.add_argument("--seeded", action="store_true",
                     help="request i carries seed i (without --device-sampler seeded requests run one step at a time)")
+    ap.add_argument("--device-logit-ops", action="store_true",
+                    help="with --device-sampler: penalties and logprobs (k <= 32) on the device, in the step's own "
+                         "launches (EngineConfig.device_logit_ops; A/B against the per-request torch routes, which "
+                         "run one step at a time)")
+    ap.add_argument("--logprobs", type=int, default=None, help="every request asks for this many top logprobs")
+    ap.add_argument("--presence-penalty", type=float, default=0.0, help="every request's presence penalty")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0, help="every request's frequency penalty")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="every request's repetition penalty")
     ap.add_argument("--shared-prefix", type=int, default=0,
                     help="the first N prompt tokens are common to every request (a system prompt)")
     ap.add_argument("--request-rate", type=float, default=0.0,

@@ -24,6 +24,7 @@ import torch
 
 from kgs.models.llama import LlamaConfig
 from kgs.ops.decode import PAGE, PagedKVCache
+from kgs.ops.transformer import LOGPROB_KMAX
 
 from .model import ServingModel, gate_up_panel_widths
 from .trace import TRACE
@@ -85,6 +86,7 @@ class EngineConfig:
     paged_prefill: bool = False       # mixed steps: all prompt chunks in one attention launch over the bf16 pages
     overlap: bool = True              # plan/launch step t+1 before step t's tokens are read back (LLMEngine.step)
     device_sampler: bool = False      # temperature / top-k / top-p / seeds: one sample_rows launch per step (kgs, GPU)
+    device_logit_ops: bool = False    # penalties from a device count table + logprobs (k <= 32) in the step's launches
     seed: int = 0
 
 
@@ -112,8 +114,19 @@ def _bucket(n: int, cap: int) -> int:
 
 
 class LLMEngine:
+    # EngineConfig.device_logit_ops (off: none of these is touched)
+    device_logit_ops = False
+    _counts = None   # CountTable: the penalised requests' token-count rows on the device
+    _pen_buf = None  # [max_batch, vocab] bf16: the step's penalised logits
+    _lp = None       # logprob_rows' outputs: one packed device buffer + two pinned host buffers
+    _lp_big = frozenset()  # requests with logprobs > LOGPROB_KMAX: the blocking torch route
+    _lp_rows: dict = {}    # {row: k} of the step being sampled: the rows logprob_rows serves
+
     def __init__(self, model_cfg: LlamaConfig, cfg: EngineConfig | None = None, device="cuda", backend: str = "kgs"):
         self.cfg = cfg = cfg or EngineConfig()
+        if cfg.device_logit_ops and not cfg.device_sampler:
+            raise ValueError("device_logit_ops=True needs device_sampler=True: the penalised logits and the count "
+                             "table are consumed and updated by the device sampler's step")
         if cfg.paged_prefill and cfg.kv_cache_dtype == "fp8":
             raise ValueError("paged_prefill reads bf16 KV pages: kv_cache_dtype='fp8' keeps the gather path")
         from kgs._native import _serve
@@ -169,6 +182,9 @@ class LLMEngine:
         # EngineConfig.device_sampler: like paged_prefill, only the kgs backend on a GPU has the kernel
         self.device_sampler = cfg.device_sampler and backend == "kgs" and self.device.type == "cuda"
         self._draw = None  # the sampler's per-row parameters: two packed pinned host buffers + one on the device
+        # EngineConfig.device_logit_ops: only where the device sampler runs
+        self.device_logit_ops = cfg.device_logit_ops and self.device_sampler
+        self._lp_big = set()
 
     def _pages_from_memory(self, mc: LlamaConfig) -> int:
         if self.device.type != "cuda":
@@ -205,6 +221,8 @@ class LLMEngine:
         # plain-sampling batch skips those scans entirely)
         if params.logprobs is not None:
             self._want_lp.add(rid)
+            if self.device_logit_ops and params.logprobs > LOGPROB_KMAX:
+                self._lp_big.add(rid)
         if params.presence_penalty or params.frequency_penalty or params.repetition_penalty != 1.0:
             self._want_pen.add(rid)
         if params.seed is not None:
@@ -215,14 +233,22 @@ class LLMEngine:
         return rid
 
     def abort(self, rid: int) -> None:
-        self._want_lp.discard(rid)
-        self._want_pen.discard(rid)
-        self._seeded.discard(rid)
-        self._watch_eos.discard(rid)
+        self._forget(rid)
         if self.sched.abort(rid):
             r = self.requests[rid]
             r.finished, r.finish_reason, r.t_done = True, "abort", time.perf_counter()
             self.sched.release(rid)
+
+    def _forget(self, rid: int) -> None:
+        """A finished or aborted request leaves the per-step scans and gives its count-table slot back."""
+        self._want_lp.discard(rid)
+        self._want_pen.discard(rid)
+        self._seeded.discard(rid)
+        self._watch_eos.discard(rid)
+        if self.device_logit_ops:
+            self._lp_big.discard(rid)
+            if self._counts is not None:
+                self._counts.release(rid)
 
     def has_work(self) -> bool:
         return self._inflight is not None or self.sched.num_waiting + self.sched.num_running > 0
@@ -233,7 +259,12 @@ class LLMEngine:
         state (the output so far, per-request generators), so a batch holding
         any of them runs one step at a time. The device sampler draws a seeded
         row from (seed, tokens sampled so far), both known ahead of the tokens:
-        with it seeded requests overlap like any other."""
+        with it seeded requests overlap like any other. With device_logit_ops
+        penalties read a count table the sampling step itself updates and
+        logprobs (k <= 32) ride the token read-back: only a request asking for
+        more than 32 logprobs still takes the blocking route."""
+        if self.device_logit_ops:
+            return self.overlap and not self._lp_big
         seeded = self._seeded and not self.device_sampler
         return self.overlap and not (self._want_lp or self._want_pen or seeded)
 
@@ -302,8 +333,9 @@ class LLMEngine:
         if t is not None:
             t += [time.perf_counter()] * (4 - len(t))  # 3: launch
         toks_dev = self._sample(ids, logits)
+        lpd = self._logprobs_device(ids, logits, toks_dev) if self.device_logit_ops else None
         if self._overlap_now():
-            self._inflight = self._launch_readback(ids, toks_dev, nstep)
+            self._inflight = self._launch_readback(ids, toks_dev, nstep, lpd)
             if t is not None:
                 t.append(time.perf_counter())  # 4: sampler + read-back launch
             out = self._complete(prev, advanced, t) if prev is not None else []
@@ -311,6 +343,8 @@ class LLMEngine:
                 ph.append((plan.kind, *[round((b - a) * 1e6, 1) for a, b in zip(t, t[1:])]))
             return out
         lps = self._logprobs(ids, logits, toks_dev)
+        if lpd is not None:
+            lps = {**(lps or {}), **self._lp_tuples(lpd, self._lp["dev"].cpu().numpy())}
         toks = toks_dev.cpu().numpy().astype(np.int32)
         TRACE.mark(f"step {nstep} end")
         self._tq_check(nstep, plan.kind)
@@ -319,15 +353,21 @@ class LLMEngine:
         return self._emit(ids, toks, eos, done, lps)
 
     # ------------------------------------------------------- step helpers
-    def _launch_readback(self, ids, toks_dev: torch.Tensor, nstep: int) -> dict:
-        """Start the copy of an in-flight step's tokens to the host."""
-        cur = {"ids": ids, "dev": toks_dev, "nstep": nstep, "event": None}
+    def _launch_readback(self, ids, toks_dev: torch.Tensor, nstep: int, lpd: dict | None = None) -> dict:
+        """Start the copy of an in-flight step's tokens to the host, and of its
+        device logprobs (``lpd``: _logprobs_device's rows) with them."""
+        cur = {"ids": ids, "dev": toks_dev, "nstep": nstep, "event": None, "lp_rows": lpd, "lp_host": None}
         if toks_dev.is_cuda:
             if self._pinned is None:
                 self._pinned = [torch.empty(self.cfg.max_batch, dtype=torch.int64).pin_memory() for _ in range(2)]
             buf = self._pinned[self._flip][:len(ids)]
             self._flip ^= 1
             buf.copy_(toks_dev, non_blocking=True)
+            if lpd is not None:
+                lp = self._lp
+                cur["lp_host"] = lp["host"][lp["flip"]]
+                lp["flip"] ^= 1
+                cur["lp_host"].copy_(lp["dev"], non_blocking=True)
             cur["host"], cur["event"] = buf, torch.cuda.Event()
             cur["event"].record()
         else:
@@ -362,7 +402,8 @@ class LLMEngine:
                 rid = int(ids[j])
                 if rid not in done and self.sched.abort(rid):
                     done.add(rid)
-        out = self._emit(ids, toks, eos, done, None)
+        lps = self._lp_tuples(cur["lp_rows"], cur["lp_host"].numpy()) if cur.get("lp_host") is not None else None
+        out = self._emit(ids, toks, eos, done, lps)
         if t is not None:
             t.append(time.perf_counter())  # 6: result loop
         return out
@@ -432,10 +473,7 @@ class LLMEngine:
             fin = rid in done
             if fin:
                 r.finished, r.t_done = True, now
-                self._want_lp.discard(rid)
-                self._want_pen.discard(rid)
-                self._seeded.discard(rid)
-                self._watch_eos.discard(rid)
+                self._forget(rid)
                 r.finish_reason = "stop" if eos[j] else "length"
                 self.sched.release(rid)
             out.append((rid, int(toks[j]), fin))
@@ -621,6 +659,8 @@ class LLMEngine:
         if not self._want_lp:
             return None
         rows = [j for j, r in enumerate(ids) if int(r) in self._want_lp]
+        if self.device_logit_ops:  # logprob_rows served the others
+            rows = [j for j in rows if int(ids[j]) in self._lp_big]
         if not rows:
             return None
         sel = torch.as_tensor(rows, device=logits.device)
@@ -679,23 +719,36 @@ class LLMEngine:
         neither depends on its batch mates or on a token not yet read back.
         Penalised rows are computed in fp32 as on the torch route and rounded
         back to bf16 (one extra rounding of those rows' logits); every row then
-        takes the kernel."""
+        takes the kernel. With EngineConfig.device_logit_ops the penalties are
+        three launches around the sampler instead, whatever the number of
+        penalised rows: penalize_rows writes the step's penalised logits into an
+        engine-owned buffer from the device count table (kgs.serve.count_table),
+        sample_rows draws from that buffer, token_counts_add counts the drawn
+        tokens. A step without a penalised row is unchanged."""
         from kgs.ops.transformer import sample_rows
 
         if not (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2):
             raise RuntimeError(f"device_sampler needs bf16 GPU logits [rows, vocab], got {logits.dtype} "
                                f"{tuple(logits.shape)} on {logits.device}")
-        rows, sub = self._penalized_rows(ids, logits)
-        if rows:
-            logits = logits.clone()
-            logits[rows] = sub.to(torch.bfloat16)
+        if not self.device_logit_ops:
+            rows, sub = self._penalized_rows(ids, logits)
+            if rows:
+                logits = logits.clone()
+                logits[rows] = sub.to(torch.bfloat16)
         n, mb = len(ids), self.cfg.max_batch
         if self._draw is None:
             # per buffer: seed i64[mb] | counter i64[mb] | temperature f32[mb] | top_k i32[mb] | top_p f32[mb]
+            # | device_logit_ops: freq f32[mb] | pres f32[mb] | rep f32[mb] | slot i32[mb] | want i32[mb]
             offs = {"seed": (0, np.int64), "counter": (8 * mb, np.int64), "temperature": (16 * mb, np.float32),
                     "top_k": (20 * mb, np.int32), "top_p": (24 * mb, np.float32)}
-            host = [torch.zeros(28 * mb, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            dev = torch.zeros(28 * mb, dtype=torch.uint8, device=self.device)
+            size = 28 * mb
+            if self.device_logit_ops:
+                for k, dt in (("freq", np.float32), ("pres", np.float32), ("rep", np.float32), ("slot", np.int32),
+                              ("want", np.int32)):
+                    offs[k] = (size, dt)
+                    size += 4 * mb
+            host = [torch.zeros(size, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            dev = torch.zeros(size, dtype=torch.uint8, device=self.device)
             tdt = {np.int64: torch.int64, np.float32: torch.float32, np.int32: torch.int32}
             self._draw = {
                 "host": host, "dev": dev, "flip": 0,
@@ -713,11 +766,80 @@ class LLMEngine:
         hn["counter"][:n] = [r.sampled for r in reqs]
         for r in reqs:
             r.sampled += 1
+        pen = self.device_logit_ops and self._stage_logit_ops(reqs, hn, logits.shape[1])
         d["dev"].copy_(d["host"][d["flip"]], non_blocking=True)
         d["flip"] ^= 1
         v = d["views"]
-        return sample_rows(logits, v["temperature"][:n], v["top_k"][:n], v["top_p"][:n], v["seed"][:n],
+        if pen:
+            from kgs.ops.transformer import penalize_rows, token_counts_add
+
+            if self._pen_buf is None:
+                self._pen_buf = torch.empty((mb, logits.shape[1]), dtype=torch.bfloat16, device=self.device)
+            logits = penalize_rows(logits, v["freq"][:n], v["pres"][:n], v["rep"][:n], v["slot"][:n],
+                                   self._counts.table, out=self._pen_buf[:n])
+        toks = sample_rows(logits, v["temperature"][:n], v["top_k"][:n], v["top_p"][:n], v["seed"][:n],
                            v["counter"][:n])
+        if pen:  # the sampled tokens join their requests' counts before the next step reads them
+            token_counts_add(self._counts.table, toks, v["slot"][:n])
+        return toks
+
+    def _stage_logit_ops(self, reqs, hn, vocab: int) -> bool:
+        """The step's per-row penalty parameters, count-table slots and logprob
+        wishes into the packed parameter buffer; a penalised request takes its
+        slot here, the first time it is sampled. Returns whether any row is
+        penalised; the rows that want logprobs are left in self._lp_rows."""
+        n = len(reqs)
+        hn["slot"][:n] = -1
+        hn["want"][:n] = -1
+        pen = False
+        self._lp_rows = {}
+        for j, r in enumerate(reqs if (self._want_pen or self._want_lp) else ()):
+            p = r.params
+            if r.id in self._want_pen:
+                if self._counts is None:
+                    from .count_table import CountTable
+
+                    self._counts = CountTable(vocab, self.device)
+                hn["slot"][j] = self._counts.acquire(r.id, r.prompt, r.output)
+                hn["freq"][j], hn["pres"][j], hn["rep"][j] = p.frequency_penalty, p.presence_penalty, \
+                    p.repetition_penalty
+                pen = True
+            if r.id in self._want_lp and r.id not in self._lp_big:
+                hn["want"][j] = self._lp_rows[j] = int(p.logprobs)
+        return pen
+
+    def _logprobs_device(self, ids, logits: torch.Tensor, toks: torch.Tensor) -> dict | None:
+        """EngineConfig.device_logit_ops: one logprob_rows launch on the step's raw
+        logits for the rows that want at most 32 logprobs ({row: k}; None when no
+        row does). The results stay on the device in one packed buffer,
+        lp f32[mb] | top_val f32[mb, 32] | top_idx i32[mb, 32]: _launch_readback
+        copies it to pinned memory with the tokens, _lp_tuples reads it."""
+        rows = self._lp_rows
+        if not rows:
+            return None
+        from kgs.ops.transformer import logprob_rows
+
+        n, mb = len(ids), self.cfg.max_batch
+        if self._lp is None:
+            size = 4 * mb * (1 + 2 * LOGPROB_KMAX)
+            self._lp = {"dev": torch.zeros(size, dtype=torch.uint8, device=self.device), "flip": 0,
+                        "host": [torch.zeros(size, dtype=torch.uint8).pin_memory() for _ in range(2)]}
+        lp, tv, ti = self._lp_views(self._lp["dev"])
+        logprob_rows(logits, toks, self._draw["views"]["want"][:n], lp[:n], tv[:n], ti[:n])
+        return rows
+
+    def _lp_views(self, buf):
+        """(lp [mb], top_val [mb, 32], top_idx [mb, 32]) of a packed logprob buffer (a tensor or a numpy array)."""
+        mb, f32, i32 = self.cfg.max_batch, *((torch.float32, torch.int32) if isinstance(buf, torch.Tensor)
+                                             else (np.float32, np.int32))
+        a, b = 4 * mb, 4 * mb * (1 + LOGPROB_KMAX)
+        return (buf[:a].view(f32), buf[a:b].view(f32).reshape(mb, LOGPROB_KMAX),
+                buf[b:].view(i32).reshape(mb, LOGPROB_KMAX))
+
+    def _lp_tuples(self, rows: dict, buf: np.ndarray) -> dict:
+        """{row: (logprob, [(token, logprob)] top-k)} from a packed logprob buffer on the host."""
+        lp, tv, ti = self._lp_views(buf)
+        return {j: (float(lp[j]), list(zip(ti[j, :k].tolist(), tv[j, :k].tolist()))) for j, k in rows.items()}
 
     def _sample(self, ids, logits: torch.Tensor) -> torch.Tensor:
         if self.device_sampler:
