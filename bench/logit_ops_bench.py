@@ -2,12 +2,13 @@
 against ``EngineConfig.device_logit_ops`` (``penalize_rows``, ``token_counts_add``,
 ``logprob_rows``), same logits, same process, ``device_sampler`` on both sides.
 
-Both routes are the engine's own code on a bare engine object (no model, no
-scheduler) holding the step's requests. Off: ``_sample`` (``_penalized_rows``, the
-clone, ``sample_rows``) then the blocking ``_logprobs``. On: ``_sample`` (the three
-launches around the sampler), ``_logprobs_device`` and the read-back launch; each
-step then turns the step before's pinned results into tuples, as overlapped
-engine steps do. So the figures include the host's share of both.
+Both routes are the engine's own code: ``Sampler.sample``
+(``kgs.serve.sampling``) on two samplers (no model, no scheduler) over the
+step's requests, the flag differing. Off: the per-request penalties on the host,
+the clone, ``sample_rows`` and the blocking ``log_softmax`` route. On: the three
+launches around the sampler and ``logprob_rows``; each step then reads the
+result of the step before, as overlapped engine steps do. Both end in the
+read-back launch. So the figures include the host's share of both.
 
 Rounds interleave the routes; each round times ``--iters`` back-to-back steps
 with a host clock around work that ends in a device synchronise. Figures are
@@ -40,65 +41,47 @@ CASES = {"penalties, every row": ("all", None), "penalties, one row": ("one", No
 HISTORY, PROMPT_LEN, TOP = 256, 512, 5
 
 
-def bare_engine(rows: int, pen, lp, device_logit_ops: bool):
-    """An LLMEngine with just what the sampling and logprob steps read."""
-    from kgs.serve.engine import EngineConfig, LLMEngine, Request, SamplingParams
+def sampler(rows: int, pen, lp, device_logit_ops: bool):
+    """A Sampler over the requests of one step."""
+    from kgs.serve.engine import EngineConfig, Request, SamplingParams
+    from kgs.serve.sampling import Sampler
 
-    eng = object.__new__(LLMEngine)
-    eng.cfg = EngineConfig(max_batch=max(ROWS), device_sampler=True, device_logit_ops=device_logit_ops)
-    eng.device, eng.backend = torch.device("cuda"), "kgs"
-    eng.device_sampler, eng._draw = True, None
-    eng.device_logit_ops, eng._lp_big = device_logit_ops, set()
-    eng._want_pen, eng._seeded, eng._want_lp = set(), set(), set()
-    eng._pinned, eng._flip = None, 0
-    eng.requests = {}
+    requests = {}
+    s = Sampler(EngineConfig(max_batch=max(ROWS), device_sampler=True, device_logit_ops=device_logit_ops), "cuda",
+                "kgs", VOCAB, requests)
     rng = np.random.default_rng(rows)
     for rid in range(rows):
         kw = {}
         if pen == "all" or (pen == "one" and rid == 0):
             kw.update(frequency_penalty=0.5, presence_penalty=0.3, repetition_penalty=1.2)
-            eng._want_pen.add(rid)
         if lp == "all" or (lp == "one" and rid == 0):
             kw.update(logprobs=TOP)
-            eng._want_lp.add(rid)
-        p = SamplingParams(temperature=0.8, **kw)
-        eng.requests[rid] = Request(rid, rng.integers(3, VOCAB, PROMPT_LEN).tolist(), p,
-                                    output=rng.integers(3, VOCAB, HISTORY).tolist(), draw=(0.8, 0, 1.0, rid + 1))
-    return eng
+        requests[rid] = Request(rid, rng.integers(3, VOCAB, PROMPT_LEN).tolist(), SamplingParams(temperature=0.8, **kw),
+                                output=rng.integers(3, VOCAB, HISTORY).tolist())
+        s.track(requests[rid])
+    return s
 
 
-def step_off(eng, ids, logits):
-    toks = eng._sample(ids, logits)
-    return toks, eng._logprobs(ids, logits, toks)
-
-
-def step_on(eng, ids, logits, state):
+def step_on(s, ids, logits, state):
     """One overlapped step: launch, then complete the step before."""
-    toks = eng._sample(ids, logits)
-    cur = eng._launch_readback(ids, toks, 0, eng._logprobs_device(ids, logits, toks))
-    prev, state["cur"] = state.get("cur"), cur
-    lps = None
-    if prev is not None:
-        prev["event"].synchronize()
-        if prev["lp_host"] is not None:
-            lps = eng._lp_tuples(prev["lp_rows"], prev["lp_host"].numpy())
-    return toks, lps
+    prev, state["cur"] = state.get("cur"), s.sample(ids, logits)
+    return prev.result() if prev is not None else None
 
 
-def kernels_only(eng, ids, logits) -> dict:
+def kernels_only(s, ids, logits, lp) -> dict:
     """Each new kernel alone on what the device route staged."""
     from kgs.ops.transformer import logprob_rows, penalize_rows, token_counts_add
 
-    n, v = len(ids), eng._draw["views"]
+    n, v = len(ids), s.params.dev
     out = {}
     toks = torch.zeros(n, dtype=torch.int64, device="cuda")
-    if eng._counts is not None:
-        table, buf = eng._counts.table, eng._pen_buf[:n]
+    if s.counts is not None:
+        table, buf = s.counts.table, torch.empty_like(logits)
         out["penalize_rows"] = lambda: penalize_rows(logits, v["freq"][:n], v["pres"][:n], v["rep"][:n],
                                                      v["slot"][:n], table, out=buf)
         out["token_counts_add"] = lambda: token_counts_add(table, toks, v["slot"][:n])
-    if eng._lp is not None:
-        lp, tv, ti = eng._lp_views(eng._lp["dev"])
+    if lp is not None:
+        lp, tv, ti = (s.lp.dev[k] for k in ("lp", "top_val", "top_idx"))
         out["logprob_rows"] = lambda: logprob_rows(logits, toks, v["want"][:n], lp[:n], tv[:n], ti[:n])
     return out
 
@@ -116,9 +99,9 @@ def main(argv=None) -> int:
                   * a.scale).bfloat16()
         ids = np.arange(rows)
         for name, (pen, lp) in CASES.items():
-            off, on = bare_engine(rows, pen, lp, False), bare_engine(rows, pen, lp, True)
+            off, on = sampler(rows, pen, lp, False), sampler(rows, pen, lp, True)
             state = {}
-            routes = {"off_us": lambda: step_off(off, ids, logits), "on_us": lambda: step_on(on, ids, logits, state)}
+            routes = {"off_us": lambda: off.sample(ids, logits), "on_us": lambda: step_on(on, ids, logits, state)}
             for fn in routes.values():  # warm-up: buffers, the count-table rows, code objects
                 fn()
                 fn()
@@ -133,7 +116,7 @@ def main(argv=None) -> int:
                         for r, v in times.items()})
             rec["on_over_off"] = round(rec["on_us"] / rec["off_us"], 4)
             rec["kernel_us"] = {k: round(statistics.median(timed_events(fn, a.iters) for _ in range(a.rounds)), 1)
-                                for k, fn in kernels_only(on, ids, logits).items()}
+                                for k, fn in kernels_only(on, ids, logits, lp).items()}
             res.append(rec)
             print(json.dumps(rec), flush=True)
             del off, on, state, routes

@@ -1,11 +1,12 @@
 """Per-step sampler time: the engine's torch route against the device sampler
 (``sample_rows``), same logits, same process.
 
-Both routes are the engine's own code: ``LLMEngine._sample`` is called on a
-bare engine object (no model, no scheduler) holding the step's requests, once
-with ``device_sampler`` off (the chain of torch ops: cast, divide, topk, sort,
-softmax, cumsum, scatter, multinomial, where) and once with it on (the packed
-parameter buffer, one copy, one launch). So the figures include the host's
+Both routes are the engine's own code: ``Sampler.sample``
+(``kgs.serve.sampling``) is called on a sampler (no model, no scheduler) over
+the step's requests, once with ``device_sampler`` off (the chain of torch ops:
+cast, divide, topk, sort, softmax, cumsum, scatter, multinomial, where) and
+once with it on (the packed parameter buffer, one copy, one launch); either
+ends in the launch of the tokens' read-back. So the figures include the host's
 share: the small tensors the torch route builds from Python lists, the
 parameter staging of the device route.
 
@@ -39,22 +40,19 @@ CASES = {"temperature": (0, 1.0, False), "top_k 50": (50, 1.0, False), "top_p 0.
          "top_k 50 + top_p 0.9": (50, 0.9, False), "top_p 0.9, half greedy": (0, 0.9, True)}
 
 
-def bare_engine(rows: int, top_k: int, top_p: float, half_greedy: bool, device_sampler: bool, temperature=0.8):
-    """An LLMEngine with just what ``_sample`` reads: the requests of one step."""
-    from kgs.serve.engine import EngineConfig, LLMEngine, Request, SamplingParams
+def sampler(rows: int, top_k: int, top_p: float, half_greedy: bool, device_sampler: bool, temperature=0.8):
+    """A Sampler over the requests of one step."""
+    from kgs.serve.engine import EngineConfig, Request, SamplingParams
+    from kgs.serve.sampling import Sampler
 
-    eng = object.__new__(LLMEngine)
-    eng.cfg = EngineConfig(max_batch=max(ROWS), device_sampler=device_sampler)
-    eng.device, eng.backend = torch.device("cuda"), "kgs"
-    eng.device_sampler, eng._draw = device_sampler, None
-    eng._want_pen, eng._seeded, eng._want_lp = set(), set(), set()
-    eng._gen = torch.Generator(device="cuda").manual_seed(0)
-    eng.requests = {}
+    requests = {}
+    s = Sampler(EngineConfig(max_batch=max(ROWS), device_sampler=device_sampler), "cuda", "kgs", VOCAB, requests)
     for rid in range(rows):
         greedy = half_greedy and rid % 2 == 1
         p = SamplingParams(temperature=0.0 if greedy else temperature, top_k=top_k, top_p=top_p)
-        eng.requests[rid] = Request(rid, [1], p, draw=(p.temperature, top_k, top_p, rid + 1))
-    return eng
+        requests[rid] = Request(rid, [1], p)
+        s.track(requests[rid])
+    return s
 
 
 def timed(fn, iters):
@@ -76,12 +74,12 @@ def timed_events(fn, iters):
     return 1e3 * a.elapsed_time(b) / iters
 
 
-def kernel_only(eng, ids, logits):
+def kernel_only(s, ids, logits):
     """sample_rows alone on the parameters the device route staged (device events
     around back-to-back launches): the GPU's share of device_us."""
     from kgs.ops.transformer import sample_rows
 
-    n, v = len(ids), eng._draw["views"]
+    n, v = len(ids), s.params.dev
     args = [v[k][:n] for k in ("temperature", "top_k", "top_p", "seed", "counter")]
     out = torch.empty(n, dtype=torch.int64, device="cuda")
     return lambda: sample_rows(logits, *args, out=out)
@@ -102,8 +100,8 @@ def main(argv=None) -> int:
                   * a.scale).bfloat16()
         ids = np.arange(rows)
         for name, (k, p, half) in CASES.items():
-            engs = {"torch_us": bare_engine(rows, k, p, half, False), "device_us": bare_engine(rows, k, p, half, True)}
-            routes = {r: (lambda e=e: e._sample(ids, logits)) for r, e in engs.items()}
+            engs = {"torch_us": sampler(rows, k, p, half, False), "device_us": sampler(rows, k, p, half, True)}
+            routes = {r: (lambda e=e: e.sample(ids, logits).tokens) for r, e in engs.items()}
             toks = {r: fn() for r, fn in routes.items()}  # warm-up
             torch.cuda.synchronize()
             assert all(((t >= 0) & (t < VOCAB)).all() for t in toks.values())
@@ -123,7 +121,7 @@ def main(argv=None) -> int:
             print(json.dumps(rec), flush=True)
         del logits
         torch.cuda.empty_cache()
-    doc = {"bench": "sampler per step: LLMEngine._sample, torch route vs device_sampler",
+    doc = {"bench": "sampler per step: Sampler.sample, torch route vs device_sampler",
            "device": torch.cuda.get_device_name(0), "rounds": a.rounds, "iters": a.iters, "logit_scale": a.scale,
            "cases": res}
     if a.out:

@@ -79,7 +79,7 @@ def main(argv=None) -> int:
     if not a.no_graphs:
         eng.warmup(widths=_graph_widths(a))
     last = {}
-    real_sample = eng._sample
+    real_sample = eng.sampler.sample
 
     def sample(ids, logits):  # keep a checksum of every step's logits
         lf = logits.float()
@@ -87,7 +87,7 @@ def main(argv=None) -> int:
         last["nan"] = last.get("nan", 0) + int(torch.isnan(lf).sum().item())
         return real_sample(ids, logits)
 
-    eng._sample = sample
+    eng.sampler.sample = sample
     prompts = _prompts(a.requests, a.input_len, mc.vocab, seed=3)
     outs = eng.generate(prompts, SamplingParams(max_tokens=a.output_len, ignore_eos=True))
     torch.cuda.synchronize()

@@ -162,7 +162,7 @@ def test_engine_flag_defaults_off_needs_the_device_sampler_and_is_ignored_by_the
             assert not eng._overlap_now()  # penalties / logprobs: still one step at a time
             eng.abort(rid)
         outs = eng.generate(prompts, ps)
-        assert eng._counts is None  # no count table on this route
+        assert eng.sampler.counts is None  # no count table on this route
         return [(r.output, r.logprobs) for r in outs]
 
     on, off = run(True), run(False)

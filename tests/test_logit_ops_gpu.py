@@ -305,7 +305,7 @@ def _batched(overlap: bool, num_pages: int = 256, newest: int = LP):
     outs = eng.generate([_prompts()[j] for j in order], [_params()[j] for j in order])
     outs = [outs[order.index(j)] for j in range(4)]
     assert [len(r.output) for r in outs] == [8] * 4 and [len(r.logprobs) for r in outs] == [0, 0, 0, 8]
-    assert eng._counts is not None and eng._counts.used == 0  # every slot is free again
+    assert eng.sampler.counts is not None and eng.sampler.counts.used == 0  # every slot is free again
     return _result(outs), dict(eng.stats)
 
 
@@ -330,7 +330,7 @@ def test_engine_mixed_batch_is_the_same_overlapped_sequential_alone_and_preempte
         eng = _engine(overlap=True)
         alone = _result(eng.generate(_prompts()[j:j + 1], _params()[j:j + 1]))
         assert alone[0] == on[j], j
-        assert eng._counts is None or eng._counts.used == 0
+        assert eng.sampler.counts is None or eng.sampler.counts.used == 0
     # 6 usable pages for 4 sequences that need 8: preemption + recompute
     pre, stats = _batched(True, num_pages=7, newest=PEN)
     assert stats["preemptions"] >= 1
@@ -355,7 +355,7 @@ def test_engine_penalised_and_logprob_requests_stay_overlapped():
         if eng.has_work():
             assert eng._overlap_now() and eng._inflight is not None
             seen += 1
-    assert seen >= 6 and eng._counts.used == 0
+    assert seen >= 6 and eng.sampler.counts.used == 0
     assert [len(eng.requests[r].output) for r in rids] == [8] * 4
     # more than 32 logprobs: the blocking route, one step at a time, for as long as that request runs
     eng = _engine(overlap=True)
@@ -381,14 +381,14 @@ def test_engine_strong_presence_penalty_never_repeats_and_abort_frees_the_slot()
     # an EOS the request samples as its third token: seen one step late, the extra step's token is dropped
     eng = _engine(overlap=True, eos_token_id=out[2])
     r = eng.generate(_prompts()[:1], [dataclasses.replace(p, ignore_eos=False)])[0]
-    assert r.output == out[:3] and r.finish_reason == "stop" and eng._counts.used == 0
+    assert r.output == out[:3] and r.finish_reason == "stop" and eng.sampler.counts.used == 0
     eng = _engine(overlap=False)
     rid = eng.add_request(_prompts()[1], p)
     for _ in range(3):
         eng.step()
-    assert eng._counts.used == 1 and eng._counts.slot(rid) >= 0
+    assert eng.sampler.counts.used == 1 and eng.sampler.counts.slot(rid) >= 0
     eng.abort(rid)
-    assert eng._counts.used == 0 and not eng.has_work()
+    assert eng.sampler.counts.used == 0 and not eng.has_work()
 
 
 def test_engine_unpenalised_greedy_tokens_equal_the_flag_off_engine_and_the_argmax():

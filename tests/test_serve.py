@@ -555,19 +555,9 @@ def test_http_n_samples():
 def test_sampling_penalties():
     from kgs.serve import EngineConfig, LLMEngine, SamplingParams
 
+    # (the penalty arithmetic itself: tests/test_sampling_stage.py)
     eng = LLMEngine(_tiny(), EngineConfig(num_pages=32, max_batch=4, max_model_len=256, cuda_graphs=False),
                     device="cpu", backend="ref")
-    rid = eng.add_request([5, 6], SamplingParams(max_tokens=1, presence_penalty=1.0, frequency_penalty=0.5,
-                                                 repetition_penalty=2.0))
-    eng.abort(rid)  # keep it out of the scheduler; drive the sampler by hand
-    eng._want_pen.add(rid)
-    r = eng.requests[rid]
-    r.output = [7, 7, 9]
-    logits = torch.zeros(1, 16)
-    logits[0, 5], logits[0, 7], logits[0, 9], logits[0, 3] = 4.0, 4.0, -2.0, 1.0
-    out = eng._penalize([rid], logits)[0]
-    # 7: (4 - 0.5*2 - 1) / 2 = 1; 9: (-2 - 0.5 - 1) * 2 = -7; 5 (prompt): 4 / 2 = 2; 3 untouched
-    assert out[7].item() == 1.0 and out[9].item() == -7.0 and out[5].item() == 2.0 and out[3].item() == 1.0
     # greedy with a strong presence penalty never repeats a generated token
     g = eng.generate([[5, 6, 7]], SamplingParams(max_tokens=12, ignore_eos=True, presence_penalty=100.0))[0]
     assert len(set(g.output)) == len(g.output)
@@ -583,7 +573,7 @@ def test_seeded_sampling_is_reproducible():
     def run(engine_seed, seed):
         eng = LLMEngine(_tiny(), EngineConfig(num_pages=64, max_batch=4, max_model_len=256, cuda_graphs=False),
                         device="cpu", backend="ref")
-        eng._gen.manual_seed(engine_seed)  # the engine-wide sampling stream (the weights stay the same)
+        eng.sampler.gen.manual_seed(engine_seed)  # the engine-wide sampling stream (the weights stay the same)
         ps = [SamplingParams(max_tokens=6, temperature=1.0, seed=seed, ignore_eos=True)] + \
              [SamplingParams(max_tokens=6, temperature=1.0, ignore_eos=True)] * 2
         return [r.output for r in eng.generate(prompts, ps)]
@@ -609,22 +599,6 @@ def test_stop_text_truncates_and_holds_back():
     st2 = StopText(tok, ["zzz"])  # never hits: everything comes out by the final token
     out2 = "".join(st2.push(t, i == len(ids) - 1)[0] for i, t in enumerate(ids))
     assert out2 == "hello world, bye"
-
-
-def test_top_p_sampling_keeps_nucleus():
-    from kgs.serve import EngineConfig, LLMEngine, SamplingParams
-
-    eng = LLMEngine(_tiny(), EngineConfig(num_pages=32, max_batch=4, max_model_len=256, cuda_graphs=False),
-                    device="cpu", backend="ref")
-    rid = eng.add_request([5, 6, 7], SamplingParams(max_tokens=1, temperature=1.0, top_p=0.3))
-    eng.abort(rid)
-    # one dominant token (p ~ 0.9) -> top_p 0.3 always picks it; top_p 1.0 can pick others
-    logits = torch.full((2, 64), -5.0)
-    logits[:, 7] = 5.0
-    eng.requests[rid].params = SamplingParams(temperature=1.0, top_p=0.3)
-    rid2 = eng.add_request([5, 6], SamplingParams(max_tokens=1, temperature=1.0, top_p=1.0))
-    picks = {int(eng._sample([rid, rid2], logits)[0]) for _ in range(50)}
-    assert picks == {7}
 
 
 def test_online_bench_poisson_cpu():
