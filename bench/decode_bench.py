@@ -169,6 +169,68 @@ def tune_gemm(iters, ms, ring_bytes=2 << 30, fp8=False):
     print("TUNED = " + repr(table), flush=True)
 
 
+def tune_mxfp4(iters, ms, ring_bytes=4 << 30, rounds=5):
+    """--tune --mxfp4: time every (variant, split-K) of the MXFP4 (W4A16) skinny
+    GEMM per Llama shape and batch bucket with HBM-streamed weights, then time
+    bf16 / fp8 / mxfp4 on their routes (skinny_config; mxfp4: the sweep's best)
+    in interleaved rounds: medians and the spread of the rounds per format.
+    Prints TUNED_MXFP4 / TUNED_TINY_MXFP4 tables for kgs/ops/decode.py."""
+    import statistics
+
+    from kgs.ops.decode import KIN_VARIANTS, PackedWeight, _mt, skinny_config, skinny_gemm, skinny_geometry, \
+        skinny_variants
+
+    table, tiny = {}, {}
+    for name, (n, k) in SHAPES.items():
+        # the 4-bit copies are a quarter of the bf16 bytes: enough of them to rotate past the 256 MB MALL
+        copies = max(2, min(64, ring_bytes // (n * k * 2)))
+        packed = {"bf16": [], "fp8": [], "mxfp4": []}
+        for _ in range(copies):
+            w = (torch.randn(n, k, device="cuda") * k ** -0.5).to(torch.bfloat16)
+            packed["bf16"].append(PackedWeight(w))
+            packed["fp8"].append(PackedWeight(w, fp8=True))
+            packed["mxfp4"].append(PackedWeight(w, mxfp4=True))
+            del w
+        for m in ms:
+            x = (torch.rand(m, k, device="cuda") * 2 - 1).to(torch.bfloat16)
+            out = torch.empty(m, n, dtype=torch.bfloat16, device="cuda")
+            it = {"i": 0}
+
+            def call(fmt, v, ks):
+                it["i"] = (it["i"] + 1) % copies
+                skinny_gemm(x, packed[fmt][it["i"]], out=out, ksplit=ks, variant=v)
+
+            res = {}
+            for v in skinny_variants(m):
+                rps, kpc, mpad = skinny_geometry(m, v)
+                if n % rps or k % kpc or not (v <= 12 or v in KIN_VARIANTS):
+                    continue
+                nch, nstrip = k // kpc, n // rps
+                for ks in [d for d in range(1, nch + 1) if nch % d == 0 and nstrip * d <= 2048 and
+                           (d == 1 or d * mpad * n * 4 <= (64 << 20))]:
+                    res[(v, ks)] = _time(lambda v=v, ks=ks: call("mxfp4", v, ks), iters)
+            (bv, bks), _ = min(res.items(), key=lambda kv: kv[1])
+            routes = {"bf16": skinny_config(m, n, k), "fp8": skinny_config(m, n, k, fp8=True), "mxfp4": (bv, bks)}
+            times = {f: [] for f in routes}
+            for _ in range(rounds):
+                for f, (v, ks) in routes.items():
+                    times[f].append(_time(lambda f=f, v=v, ks=ks: call(f, v, ks), iters))
+            if m < 16:  # few-row entries: (variant, ksplit, up to M), extended while the winner stays
+                if (n, k) not in tiny or tiny[(n, k)][:2] == (bv, bks):
+                    tiny[(n, k)] = (bv, bks, m)
+            else:
+                table[(_mt(m), n, k)] = (bv, bks)
+            print(json.dumps({"op": "skinny_tune_mxfp4", "shape": name, "m": m, "n": n, "k": k, "copies": copies,
+                              "routes": {f: list(r) for f, r in routes.items()},
+                              "us": {f: round(statistics.median(t), 2) for f, t in times.items()},
+                              "spread_us": {f: round(max(t) - min(t), 2) for f, t in times.items()},
+                              "sweep": {f"{v}/{ks}": round(t, 1) for (v, ks), t in sorted(res.items())}}), flush=True)
+        del packed
+        torch.cuda.empty_cache()
+    print("TUNED_MXFP4 = " + repr(table), flush=True)
+    print("TUNED_TINY_MXFP4 = " + repr(tiny), flush=True)
+
+
 def bench_attn(iters):
     from kgs.ops.decode import PagedKVCache, decode_splits, paged_decode_attention
 
@@ -200,6 +262,8 @@ def main(argv=None) -> int:
     ap.add_argument("--sweep", action="store_true", help="time every valid split-K factor")
     ap.add_argument("--tune", action="store_true", help="time every tile variant x split-K; print a TUNED table")
     ap.add_argument("--fp8", action="store_true", help="--tune the weight-only fp8 (W8A16) kernels")
+    ap.add_argument("--mxfp4", action="store_true",
+                    help="--tune the weight-only MXFP4 (W4A16) kernels; bf16 / fp8 / mxfp4 per launch, interleaved")
     ap.add_argument("--wide", action="store_true", help="kgs 256x256 GEMM vs hipBLASLt at M >= 128")
     ap.add_argument("--model", choices=("llama3-8b", "llama3-70b"), default="llama3-8b")
     a = ap.parse_args(argv)
@@ -208,6 +272,9 @@ def main(argv=None) -> int:
         SHAPES.update(SHAPES_70B)
     global SWEEP
     SWEEP = a.sweep
+    if a.tune and a.mxfp4:
+        tune_mxfp4(a.iters, [int(v) for v in a.ms.split(",") if int(v) <= 64])
+        return 0
     if a.tune:
         tune_gemm(a.iters, [int(v) for v in a.ms.split(",")], fp8=a.fp8)
         return 0

@@ -6,6 +6,8 @@ half of LLM serving, which is HBM-bound on the weights and the KV cache.
   skinny GEMM streams it as contiguous 1 KB wave loads straight into registers.
 * :func:`skinny_gemm` -- ``x[M, K] @ W^T`` for a decode batch ``M <= 256``
   (split-K with an in-kernel last-arriver reduction when ``N`` is small).
+* :func:`mxfp4_quantize` / :func:`mxfp4_dequantize` / :func:`pack_mxfp4` -- OCP MX
+  v1.0 MXFP4 weights for the W4A16 skinny GEMM (``PackedWeight(..., mxfp4=True)``).
 * :class:`PagedKVCache` -- ``[layers, pages, kv_heads, K|V, 32 x 128]`` bf16
   pages whose element order IS the MFMA operand order of the decode attention
   (:func:`kv_index_tables`); a 32-token page of one KV head is 16 KB.
@@ -80,6 +82,75 @@ FP8 = torch.float8_e4m3fn
 FP8_MAX = 448.0
 
 
+# OCP MX v1.0 MXFP4: e2m1 elements (sign in bit 3) with one e8m0 scale per block
+# of 32 consecutive k of a row
+MX_BLOCK = 32
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# e8m0 range that keeps every product code x 2^(e - 127) a normal bf16 number:
+# 0.5 x 2^(e - 127) >= 2^-126 and 6 x 2^(e - 127) < 2^128
+_MX_EMIN, _MX_EMAX = 2, 252
+
+
+def mxfp4_quantize(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``[N, K]`` -> (codes ``uint8 [N, K/2]``, exponents ``uint8 [N, K/32]``).
+
+    Per block of 32 consecutive k of a row: ``X = 2^(floor(log2(amax)) - 2)``,
+    stored as ``e = exponent + 127`` clamped to ``[2, 252]`` (every ``code * X``
+    is a normal bf16 number; a zero block gets 127; 255 is never produced).
+    ``|v| / X`` is rounded to nearest on {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to
+    the even code, saturating at 6; the sign bit of ``v`` (of -0 too) is bit 3.
+    Byte ``j`` of a row holds element ``2j`` in its LOW nibble and ``2j + 1`` in
+    its high nibble -- the order ``v_cvt_scalef32_pk_bf16_fp4`` reads a byte in
+    (low nibble -> first bf16; pinned on the GPU by
+    tests/test_mxfp4_gpu.py::test_element_map_exact). Exact: powers of two only."""
+    n, k = w.shape
+    if k % MX_BLOCK:
+        raise ValueError(f"mxfp4_quantize needs K % {MX_BLOCK} == 0, got {tuple(w.shape)}")
+    v = w.float().reshape(n, k // MX_BLOCK, MX_BLOCK)
+    amax = v.abs().amax(-1)
+    _, ex = torch.frexp(amax)  # amax = m * 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = torch.where(amax > 0, (ex - 3 + 127).clamp(_MX_EMIN, _MX_EMAX), torch.full_like(ex, 127))
+    a = torch.ldexp(v.abs(), (127 - e)[..., None])  # |v| / X, exact
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) +
+            (a >= 1.75).to(torch.uint8) + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) +
+            (a > 5.0).to(torch.uint8))
+    code = (code | (torch.signbit(v).to(torch.uint8) << 3)).reshape(n, k // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), e.to(torch.uint8).contiguous()
+
+
+def mxfp4_dequantize(codes: torch.Tensor, exps: torch.Tensor) -> torch.Tensor:
+    """Inverse of :func:`mxfp4_quantize`: bf16 ``[N, K]`` (every value exact)."""
+    n, kb = codes.shape
+    c = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(n, 2 * kb).long()
+    lut = torch.tensor(_E2M1 + tuple(-x for x in _E2M1), dtype=torch.float32, device=codes.device)
+    sh = (exps.to(torch.int32) - 127).repeat_interleave(MX_BLOCK, dim=1)
+    return torch.ldexp(lut[c], sh).to(torch.bfloat16)
+
+
+def pack_mxfp4(codes: torch.Tensor, exps: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Quantiser output -> the skinny GEMM's streams. Codes
+    ``uint8 [N/16, K/128, 64, 16]``: a super-fragment covers 128 k; dword ``s``
+    of lane ``g*16 + r`` holds the 8 codes ``W[16 nt + r, 128 q + 32 s + 8 g : +8]``
+    (byte ``t`` of the dword = elements ``2t, 2t + 1``, low nibble first), so a
+    wave load is a contiguous 1 KB that feeds 4 k-steps. Scales
+    ``uint8 [N/16, K/128, 16, 4]``: row ``r``'s dword, byte ``s`` = the e8m0 of
+    k-step ``4 q + s``."""
+    n, kb = codes.shape
+    k = 2 * kb
+    if n % 16 or k % 128:
+        raise ValueError(f"mxfp4 weights need N % 16 == 0 and K % 128 == 0, got [{n}, {k}]")
+    data = codes.reshape(n // 16, 16, k // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(n // 16, k // 128, 64, 16)
+    scales = exps.reshape(n // 16, 16, k // 128, 4).permute(0, 2, 1, 3)
+    return data.contiguous(), scales.contiguous()
+
+
+def unpack_mxfp4(data: torch.Tensor, scales: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    nt, q = data.shape[:2]
+    codes = data.reshape(nt, q, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(nt * 16, q * 64)
+    exps = scales.permute(0, 2, 1, 3).reshape(nt * 16, q * 4)
+    return codes.contiguous(), exps.contiguous()
+
+
 class PackedWeight:
     """A projection weight in skinny-GEMM fragment order (plus its shape).
 
@@ -88,18 +159,26 @@ class PackedWeight:
       for GEMMs that apply the norm in their epilogue (``rms=``);
     * ``fp8=True``: weight-only fp8 (W8A16): OCP e4m3 with one scale per output
       row, dequantised to bf16 in registers (half the HBM bytes per step);
+    * ``mxfp4=True``: weight-only MXFP4 (W4A16, :func:`mxfp4_quantize`): ``data``
+      is the e2m1 code stream and ``wscale`` the e8m0 block scales in
+      :func:`pack_mxfp4` order (N K/2 + N K/32 bytes), dequantised exactly in
+      registers; K % 128 == 0, not with ``fp8`` or ``rope``;
     * ``rope=(H, HKV)``: a fused qkv weight in :func:`rope_rows` order, for the
       GEMM whose epilogue applies RoPE and writes the KV cache (``rope=`` of
       :func:`skinny_gemm`); its output is in the original order."""
 
-    __slots__ = ("data", "n", "k", "swiglu", "fp8", "wscale", "rope")
+    __slots__ = ("data", "n", "k", "swiglu", "fp8", "wscale", "rope", "mxfp4")
 
     def __init__(self, w: torch.Tensor, swiglu: bool = False, fold: torch.Tensor | None = None, fp8: bool = False,
-                 rope: tuple | None = None):
+                 rope: tuple | None = None, mxfp4: bool = False):
         self.n, self.k = w.shape
-        self.swiglu, self.fp8, self.rope = swiglu, fp8, rope
+        self.swiglu, self.fp8, self.rope, self.mxfp4 = swiglu, fp8, rope, mxfp4
         if swiglu and rope:
             raise ValueError("a weight is either SwiGLU- or RoPE-packed")
+        if mxfp4 and (fp8 or rope):
+            raise ValueError("an mxfp4 weight is neither fp8 nor RoPE-packed (the RoPE epilogue is bf16-weight only)")
+        if mxfp4 and (self.n % 16 or self.k % 128):
+            raise ValueError(f"mxfp4 weights need N % 16 == 0 and K % 128 == 0, got {tuple(w.shape)}")
         rows = swiglu_rows(self.n).to(w.device) if swiglu else \
             rope_rows(self.n, *rope).to(w.device) if rope else None
         if fold is not None:
@@ -112,6 +191,11 @@ class PackedWeight:
                 q, scale = q[rows], scale[rows]
             self.data = pack_weight(q)
             self.wscale = scale.float().contiguous()
+        elif mxfp4:
+            codes, exps = mxfp4_quantize(w)
+            if rows is not None:
+                codes, exps = codes[rows], exps[rows]
+            self.data, self.wscale = pack_mxfp4(codes, exps)
         else:
             w = w.to(torch.bfloat16)
             self.data = pack_weight(w[rows] if rows is not None else w)
@@ -122,8 +206,8 @@ class PackedWeight:
         return self.n // 2 if self.swiglu else self.n
 
     def unpacked(self) -> torch.Tensor:
-        """The weight as the kernel sees it (dequantised for fp8), in original row order."""
-        p = unpack_weight(self.data)
+        """The weight as the kernel sees it (dequantised for fp8 / mxfp4), in original row order."""
+        p = mxfp4_dequantize(*unpack_mxfp4(self.data, self.wscale)) if self.mxfp4 else unpack_weight(self.data)
         if self.fp8:
             p = (p.view(FP8).float() * self.wscale[:, None]).to(torch.bfloat16)
         if self.swiglu or self.rope:
@@ -167,6 +251,16 @@ TUNED: dict = {
 # straight from L2, so x traffic grows with M); profiles/r2/skinny_kin_tune.jsonl
 TUNED_TINY: dict = {_QKV: (20, 1, 8), _GU: (20, 1, 4), _DOWN: (20, 1, 2)}
 TUNED_TINY_FP8: dict = {_GU: (21, 1, 4), _DOWN: (21, 7, 4)}
+# the same sweep for weight-only MXFP4 (--tune --mxfp4, profiles/r10/mxfp4/tune_mxfp4.jsonl;
+# few-row entries that repeat their bucket's are left out); untuned shapes take the defaults
+TUNED_TINY_MXFP4: dict = {_QKV: (20, 1, 4), _GU: (21, 1, 4)}
+TUNED_MXFP4: dict = {
+    (1, *_QKV): (21, 1), (2, *_QKV): (5, 4), (4, *_QKV): (12, 4),
+    (1, *_O): (20, 1), (2, *_O): (4, 4), (4, *_O): (10, 4),
+    (1, *_GU): (1, 1), (2, *_GU): (7, 1), (4, *_GU): (12, 1),
+    (1, *_DOWN): (21, 2), (2, *_DOWN): (5, 8), (4, *_DOWN): (12, 8),
+    (1, *_LM): (2, 1), (2, *_LM): (6, 1), (4, *_LM): (11, 1),
+}
 # the same sweep for weight-only fp8 (--tune --fp8): (variant, ksplit) per (MT, N, K)
 TUNED_FP8: dict = {
     (1, *_QKV): (20, 1), (2, *_QKV): (5, 4), (4, *_QKV): (9, 4),
@@ -332,12 +426,12 @@ def choose_ksplit(m: int, n: int, k: int, cus: int = CUS, variant: int = 0) -> i
     return best
 
 
-def skinny_config(m: int, n: int, k: int, fp8: bool = False) -> tuple[int, int]:
+def skinny_config(m: int, n: int, k: int, fp8: bool = False, mxfp4: bool = False) -> tuple[int, int]:
     """(variant, ksplit) for a skinny-GEMM call: the tuned entry, else the defaults."""
-    tiny = (TUNED_TINY_FP8 if fp8 else TUNED_TINY).get((n, k))
+    tiny = (TUNED_TINY_MXFP4 if mxfp4 else TUNED_TINY_FP8 if fp8 else TUNED_TINY).get((n, k))
     if tiny is not None and m <= tiny[2]:
         return tiny[:2]
-    hit = (TUNED_FP8 if fp8 else TUNED).get((_mt(m), n, k))
+    hit = (TUNED_MXFP4 if mxfp4 else TUNED_FP8 if fp8 else TUNED).get((_mt(m), n, k))
     if hit is not None:
         return hit
     v = _DEFAULT_VARIANT[_mt(m)]
@@ -415,8 +509,10 @@ def skinny_gemm(x: torch.Tensor, w: PackedWeight, out: torch.Tensor | None = Non
         raise ValueError(f"inner dims differ: x {tuple(x.shape)} vs W [{w.n}, {w.k}]")
     if w.fp8 and _mt(m) > 4:
         raise ValueError("fp8 (W8A16) skinny GEMM covers batches <= 64")
+    if w.mxfp4 and _mt(m) > 4:
+        raise ValueError("mxfp4 (W4A16) skinny GEMM covers batches <= 64")
     if variant == 0 and ksplit is None:
-        variant, ks = skinny_config(m, w.n, k, fp8=w.fp8)
+        variant, ks = skinny_config(m, w.n, k, fp8=w.fp8, mxfp4=w.mxfp4)
         if rope is not None and SKINNY_VARIANTS[variant][0] != 1:
             # the RoPE epilogue is built for one-tile waves (R 1): the batch's default variant
             variant = _DEFAULT_VARIANT[_mt(m)]
@@ -440,7 +536,7 @@ def skinny_gemm(x: torch.Tensor, w: PackedWeight, out: torch.Tensor | None = Non
     if (rope is not None) != bool(w.rope):
         raise ValueError("rope= needs a rope-packed qkv weight (PackedWeight(..., rope=(H, HKV))) and vice versa")
     if rope is not None:
-        if w.fp8 or resid_ss is not None:
+        if w.fp8 or w.mxfp4 or resid_ss is not None:
             raise ValueError("the RoPE epilogue is bf16-weight only and writes a fresh qkv output")
         cache = rope["cache"]
         if cache.dtype != torch.bfloat16 or not cache.is_contiguous():
@@ -456,6 +552,14 @@ def skinny_gemm(x: torch.Tensor, w: PackedWeight, out: torch.Tensor | None = Non
             rope["sin"].data_ptr(), rope["positions"].data_ptr(), rope["slots"].data_ptr(), cache.data_ptr(),
             w.rope[0], w.rope[1], _lib.stream_handle(x.device))
         _lib.check(rc, f"skinny_gemm_rope[{m}x{w.n}x{k}, variant={variant}, ksplit={ks}]")
+        return out
+    if w.mxfp4:
+        rc = _lib.lib().kgs_skinny_gemm_mxfp4_fused(
+            w.data.data_ptr(), w.wscale.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), cnt.data_ptr(), m, w.n,
+            k, x.stride(0), out.stride(0), ks, variant, epi, rms.data_ptr() if rms is not None else None,
+            resid_ss.data_ptr() if resid_ss is not None else None, zero.data_ptr() if zero is not None else None,
+            1.0 / k, float(eps), _lib.stream_handle(x.device))
+        _lib.check(rc, f"skinny_gemm[{m}x{w.n}x{k}, variant={variant}, ksplit={ks}, epi={epi}, mxfp4]")
         return out
     rc = _lib.lib().kgs_skinny_gemm_bf16_fused(
         w.data.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), cnt.data_ptr(), m, w.n, k, x.stride(0),

@@ -397,7 +397,9 @@ def main(argv=None) -> int:
                     help="overlapped engine steps: ~7 %% lower TPOT for a few ms more TTFT (a request arriving "
                          "while a step is in flight misses that step; profiles/r5/overlap/README.md)")
     ap.add_argument("--kv-cache-dtype", choices=("bf16", "fp8"), default="bf16")
-    ap.add_argument("--decode-weights", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--decode-weights", choices=("bf16", "fp8", "mxfp4"), default="bf16",
+                    help="fp8: weight-only fp8 decode copies (W8A16); mxfp4: the model's weights rounded to OCP MXFP4, "
+                         "4-bit decode copies (W4A16)")
     ap.add_argument("--prefill-weights", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: W8A8 projections in prefill and mixed (chunked-prefill) steps")
     ap.add_argument("--data-parallel", type=int, default=1,

@@ -275,8 +275,9 @@ def main(argv=None) -> int:
                     help="unsplit SwiGLU decode routes read the row-major gate|up (A/B against the panel copies)")
     ap.add_argument("--fused-max-batch", type=int, default=48,
                     help="decode batches up to this run the fused skinny-GEMM layer (0 = never)")
-    ap.add_argument("--decode-weights", choices=("bf16", "fp8"), default="bf16",
-                    help="fp8 = weight-only fp8 decode GEMMs (W8A16); the headline is bf16")
+    ap.add_argument("--decode-weights", choices=("bf16", "fp8", "mxfp4"), default="bf16",
+                    help="fp8 = weight-only fp8 decode GEMMs (W8A16); mxfp4 = MXFP4-rounded model with 4-bit decode "
+                         "GEMMs (W4A16); the headline is bf16")
     ap.add_argument("--prefill-weights", choices=("bf16", "fp8"), default="bf16",
                     help="fp8 = W8A8 prompt pass (e4m3 weights, per-row activation scales); the headline is bf16")
     ap.add_argument("--kv-cache-dtype", choices=("bf16", "fp8"), default="bf16",

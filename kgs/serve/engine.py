@@ -40,7 +40,7 @@ class EngineConfig:
     eos_token_id: int = 2
     cuda_graphs: bool = True
     fused_max_batch: int = 48         # decode batches up to this use the fused skinny-GEMM layer; above: four-wave GEMMs (measured crossover)
-    decode_weights: str = "bf16"      # "fp8": weight-only fp8 decode copies (W8A16)
+    decode_weights: str = "bf16"      # "fp8": weight-only fp8 decode copies (W8A16); "mxfp4": MXFP4 model (W4A16)
     kv_cache_dtype: str = "bf16"      # "fp8": e4m3 KV pages
     chunked_prefill: int = 0          # > 0: mixed steps of at most this many rows (prompt chunks + decodes)
     prefix_caching: bool = False      # reuse cached KV pages of shared prompt prefixes (runs on mixed steps)
@@ -124,7 +124,9 @@ class LLMEngine:
         per_layer = h * (h + 2 * kvd) + h * h + 2 * h * i + i * h
         weights = 2 * (mc.layers * per_layer + 2 * mc.vocab * h)
         # the kgs backend keeps prefill-order and prepacked decode copies of every projection
-        copies = (1.5 if self.cfg.decode_weights == "fp8" else 2) if self.cfg.packed_decode else 1
+        # (mxfp4 decode copies: 4 bits per weight plus one e8m0 byte per 32 weights)
+        dcopy = {"fp8": 0.5, "mxfp4": 0.25 + 1 / 64}.get(self.cfg.decode_weights, 1)
+        copies = 1 + dcopy if self.cfg.packed_decode else 1
         copies += 0.5 if self.cfg.prefill_weights == "fp8" else 0
         resident = weights * (copies if self.backend == "kgs" else 1)
         if self.backend == "kgs" and self.cfg.packed_decode and self.cfg.fuse_splitk and self.cfg.w4x_panels:

@@ -26,6 +26,13 @@ Two step kinds, both driven by the native scheduler's plans
 scale per output row, dequantised in registers), halving the weight bytes a
 decode step streams; prefill and batches above the fused path stay bf16.
 
+``decode_weights="mxfp4"``: every projection weight and the LM head are rounded
+to OCP MXFP4 in place (``dq(q(w))``, what loading an MXFP4 checkpoint gives)
+before any copy is made, so the oracle, the prefill GEMMs, the > 64 decode
+routes and the panel copies all carry the same values; the batch <= 64 decode
+copies hold those values' 4-bit codes (W4A16: 4.25 bits per weight, dequantised
+exactly in registers).
+
 ``kv_cache_dtype="fp8"``: e4m3 KV pages (scale 1), dequantised in the decode
 attention's registers -- half the KV bytes per decode step.
 
@@ -87,11 +94,21 @@ class ServingModel:
         self.w_lm = base.lm_head.w
         self.packed = None
         self.fused_max_batch = fused_max_batch
-        if decode_weights not in ("bf16", "fp8"):
-            raise ValueError(f"decode_weights must be bf16 or fp8, got {decode_weights!r}")
+        if decode_weights not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"decode_weights must be bf16, fp8 or mxfp4, got {decode_weights!r}")
         self.decode_fp8 = decode_weights == "fp8"
-        if self.decode_fp8:
-            self.fused_max_batch = min(fused_max_batch, 64)  # the W8A16 skinny GEMM covers M <= 64
+        self.decode_mxfp4 = decode_weights == "mxfp4"
+        if self.decode_fp8 or self.decode_mxfp4:
+            self.fused_max_batch = min(fused_max_batch, 64)  # the W8A16 / W4A16 skinny GEMMs cover M <= 64
+        if self.decode_mxfp4:
+            if backend == "kgs" and not packed_decode:
+                raise ValueError("decode_weights='mxfp4' needs the packed decode copies")
+            # one set of numbers per model: round the shared tensors themselves
+            for w in [w for lw in self.w for w in lw.values()] + [self.w_lm]:
+                w.copy_(D.mxfp4_dequantize(*D.mxfp4_quantize(w)))
+            # the decode copies quantise W * fold: the same codes only for unit norm weights
+            if not all(bool((t == 1).all()) for t in self.ln1 + self.ln2 + [self.norm]):
+                raise ValueError("decode_weights='mxfp4' needs unit RMSNorm weights (they are folded into the copies)")
         if backend == "kgs" and not packed_decode:
             # no prepacked decode copies (e.g. Llama-3-70B: one bf16 copy of the
             # weights is 141 GB): decode runs on the library/split-K GEMMs
@@ -100,18 +117,18 @@ class ServingModel:
             self.fused_max_batch = 0
             D.reserve_workspace(self.device)
         elif backend == "kgs":
-            f8 = self.decode_fp8
+            f8, f4 = self.decode_fp8, self.decode_mxfp4
             # decode copies in skinny-GEMM fragment order; the RMSNorm weights
             # in front of qkv / gate|up / lm_head are folded into them (their
             # GEMMs apply the norm in the epilogue), gate|up is SwiGLU-packed,
             # and with bf16 weights and a bf16 cache qkv is RoPE-packed (its
             # epilogue rotates q / k and writes the KV cache)
-            rope = None if f8 or kv_cache_dtype != "bf16" else (cfg.heads, cfg.kv_heads)
-            self.packed = [{"qkv": D.PackedWeight(lw["qkv"], fold=self.ln1[i], fp8=f8, rope=rope),
-                            "o": D.PackedWeight(lw["o"], fp8=f8),
-                            "gate_up": D.PackedWeight(lw["gate_up"], swiglu=True, fold=self.ln2[i], fp8=f8),
-                            "down": D.PackedWeight(lw["down"], fp8=f8)} for i, lw in enumerate(self.w)]
-            self.packed_lm = D.PackedWeight(self.w_lm, fold=self.norm, fp8=f8)
+            rope = None if f8 or f4 or kv_cache_dtype != "bf16" else (cfg.heads, cfg.kv_heads)
+            self.packed = [{"qkv": D.PackedWeight(lw["qkv"], fold=self.ln1[i], fp8=f8, rope=rope, mxfp4=f4),
+                            "o": D.PackedWeight(lw["o"], fp8=f8, mxfp4=f4),
+                            "gate_up": D.PackedWeight(lw["gate_up"], swiglu=True, fold=self.ln2[i], fp8=f8, mxfp4=f4),
+                            "down": D.PackedWeight(lw["down"], fp8=f8, mxfp4=f4)} for i, lw in enumerate(self.w)]
+            self.packed_lm = D.PackedWeight(self.w_lm, fold=self.norm, fp8=f8, mxfp4=f4)
             D.reserve_workspace(self.device)
         # split-K decode projections (qkv, o, down from batch 64 up, kgs.ops.decode
         # W4X_TUNED) read a third copy laid out tile-panel major, so each K-step's
@@ -183,7 +200,7 @@ class ServingModel:
 
                 return gemm_nt_splitk(x, w, ns)
         if decode and self.packed is not None and name in ("o", "down") and D.use_skinny(m, w.shape[0], w.shape[1]) and \
-                not (self.decode_fp8 and m > 64):
+                not ((self.decode_fp8 or self.decode_mxfp4) and m > 64):
             return D.skinny_gemm(x, self.packed[layer][name])
         # the LM head (N = 128256) from batch 128 up runs faster on the kgs
         # 256x256 GEMM than on hipBLASLt (1.09x at 128, 1.21x at 256,

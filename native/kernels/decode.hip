@@ -125,7 +125,7 @@ struct SkinnyEpi {
   float* ss_out;
   float* ss_zero;
   float inv_k, eps;
-  const float* wscale;  // W8: per packed row dequant scale
+  const float* wscale;  // e4m3: per packed row dequant scale; mxfp4: the e8m0 block-scale dwords
   // EPI_ROPE
   const float* cosv;
   const float* sinv;
@@ -139,9 +139,26 @@ struct SkinnyEpi {
 // per lane per fragment (512 B wave loads: half the HBM bytes), dequantised to
 // bf16 in registers (v_cvt_pk_f32_fp8, times the lane's row scale, RNE to
 // bf16); x, the MFMA and every epilogue stay bf16/fp32.
+//
+// MXFP4 (weight-only OCP MX fp4, "W4A16"): e2m1 codes with one e8m0 scale per 32
+// consecutive k of a row. A ring slot is a SUPER-fragment of 4 k-steps,
+// [N/16][K/128][64 lanes][16 B]: dword s of lane (g, r) holds the 8 codes
+// W[16 nt + r, 128 q + 32 s + 8 g .. +8] (low nibble first), so a wave load is
+// again a contiguous 1 KB. Scales: [N/16][K/128][16 rows] dwords, byte s = the
+// e8m0 of k-step 4 q + s. Dequant is v_cvt_scalef32_pk_bf16_fp4 (two codes ->
+// two bf16, times 2^(e - 127)): exact, so the MFMA sees the bf16 values of the
+// dequantised weight in the same k order.
+// KGS_MXFP4_RING: the mxfp4 W ring's depth in k-steps (4, 8 or 16; capped by
+// KC). 16 = 4 KB of codes in flight per wave and row tile; measured in
+// profiles/r10/mxfp4/README.md.
+#ifndef KGS_MXFP4_RING
+#define KGS_MXFP4_RING 16
+#endif
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-template <bool W8>
-using WFrag = typename std::conditional<W8, u32x2, bf16x8>::type;
+enum { WF_BF16 = 0, WF_E4M3 = 1, WF_MXFP4 = 2 };  // weight format of a skinny instantiation
+template <int WF>
+using WFrag = typename std::conditional<WF == WF_MXFP4, u32x4,
+                                        typename std::conditional<WF == WF_E4M3, u32x2, bf16x8>::type>::type;
 
 // 8 floats -> 8 OCP e4m3 bytes (saturating at +-448, RNE)
 __device__ __forceinline__ uint2 tfm_e4m3x8(const float* v) {
@@ -169,6 +186,17 @@ __device__ __forceinline__ bf16x8 dequant8(u32x2 v, float s) {
   return o;
 }
 
+// 8 e2m1 codes (one dword) x 2^(e - 127) -> 8 bf16, four conversions
+__device__ __forceinline__ bf16x8 dequant4(unsigned codes, unsigned e) {
+  const float s = __builtin_bit_cast(float, e << 23);
+  u32x4 o;
+  o[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 0));
+  o[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 1));
+  o[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 2));
+  o[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, s, 3));
+  return __builtin_bit_cast(bf16x8, o);
+}
+
 // EROPE: the EPI_ROPE instantiation (qkv of the fused decode layer only, so
 // the other projections keep the lean epilogue's registers); its RoPE tables,
 // positions and cache slots are loaded at kernel start, under the main loop.
@@ -179,18 +207,24 @@ __device__ __forceinline__ bf16x8 dequant8(u32x2 v, float s) {
 // batch-1 launch); the waves' partial tiles are summed through LDS. x comes
 // straight from global/L2 through the W ring (no LDS staging): chunk = KC
 // k-steps per wave, k_per_chunk = 4 * 32 * KC.
-template <int R, int MT, int KC_, bool W8 = false, bool EROPE = false, bool KIN = false>
+template <int R, int MT, int KC_, int WF = WF_BF16, bool EROPE = false, bool KIN = false>
 __global__ __launch_bounds__(256, (MT * KC_ > 32 || R * MT >= 16) ? 1 : 2) void skinny(const void* __restrict__ wpv, const unsigned short* __restrict__ x,
                                                  unsigned short* __restrict__ y, float* __restrict__ ws,
                                                  int* __restrict__ cnt, int M, int N, int K, long ldx, long ldy,
                                                  int ksplit, int chunks_per_split, SkinnyEpi ep) {
   using C = SkinnyCfg<MT, KC_>;
   constexpr int KC = C::KC;
+  constexpr bool W8 = WF == WF_E4M3, W4 = WF == WF_MXFP4;
   // W ring depth in k-steps (divides KC); fp8 fragments are half the bytes, so
   // twice the depth keeps the same bytes in flight (a 16-deep bf16 ring at
   // batch 1 measured the same per launch: the fixed launch / split-K costs, not
   // the bytes in flight, set a batch-1 launch's time)
-  constexpr int PF = KC < (W8 ? 16 : 8) ? KC : (W8 ? 16 : 8);
+  constexpr int PFMAX = W4 ? (KIN && KGS_MXFP4_RING < KC ? KC : KGS_MXFP4_RING) : W8 ? 16 : 8;
+  constexpr int PF = KC < PFMAX ? KC : PFMAX;
+  // mxfp4: a ring slot is a super-fragment of SPF = 4 k-steps (chunks are whole
+  // super-fragments: every eligible variant has KC % 4 == 0)
+  constexpr int SPF = W4 ? 4 : 1, NSLOT = PF / SPF;
+  static_assert(PF % SPF == 0 && KC % SPF == 0, "mxfp4: chunks of whole super-fragments");
   // the only __shared__ object (a second one can make hipcc drain vmcnt before
   // every ds_read, cdna_hip_programming.md s5 trap 4a); the split-K "last
   // arriver" flag reuses its first word after the main loop
@@ -206,13 +240,17 @@ __global__ __launch_bounds__(256, (MT * KC_ > 32 || R * MT >= 16) ? 1 : 2) void 
   const int nsteps = chunks_per_split * KC;
   const int kk0 = KIN ? (split * 4 + w) * nsteps : split * nsteps;
   const int nt0 = KIN ? strip * R : (strip * 4 + w) * R;  // first 16-row tile of this wave
-  const WFrag<W8>* wp = (const WFrag<W8>*)wpv;
-  const WFrag<W8>* wrow[R];
+  const WFrag<WF>* wp = (const WFrag<WF>*)wpv;
+  const WFrag<WF>* wrow[R];
+  const unsigned* wxrow[R];  // mxfp4: this lane's row of scale dwords, one per super-fragment
   float wsc[R];
+  const int nld = nsteps / SPF;  // ring slots' worth of this wave's K range
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    wrow[r] = wp + ((long)(nt0 + r) * nkk + kk0) * 64 + lane;
+    wrow[r] = wp + ((long)(nt0 + r) * (nkk / SPF) + kk0 / SPF) * 64 + lane;
     wsc[r] = W8 ? ep.wscale[16 * (nt0 + r) + (lane & 15)] : 1.f;
+    if constexpr (W4)
+      wxrow[r] = (const unsigned*)ep.wscale + ((long)(nt0 + r) * (nkk / 4) + kk0 / 4) * 16 + (lane & 15);
   }
   // EROPE: per (column tile c, row tile r) the lane's 4 cos / sin values and its
   // row's cache slot, fetched now so their latency hides under the main loop
@@ -270,11 +308,27 @@ __global__ __launch_bounds__(256, (MT * KC_ > 32 || R * MT >= 16) ? 1 : 2) void 
   // Every load below is unconditional (indices clamped to the last step /
   // chunk: a few redundant L2-hit reloads at the tail) so hipcc can count
   // vmcnt through the loop instead of draining the ring before each MFMA.
-  WFrag<W8> wf[PF][R];
+  WFrag<WF> wf[NSLOT][R];
+  unsigned wex[W4 ? NSLOT : 1][R];
 #pragma unroll
-  for (int p = 0; p < PF; ++p)
+  for (int p = 0; p < NSLOT; ++p)
 #pragma unroll
-    for (int r = 0; r < R; ++r) wf[p][r] = __builtin_nontemporal_load(wrow[r] + (long)min(p, nsteps - 1) * 64);
+    for (int r = 0; r < R; ++r) {
+      wf[p][r] = __builtin_nontemporal_load(wrow[r] + (long)min(p, nld - 1) * 64);
+      if constexpr (W4) wex[p][r] = __builtin_nontemporal_load(wxrow[r] + (long)min(p, nld - 1) * 16);
+    }
+  // mxfp4: k-step p of the ring = dword p % 4 (and scale byte p % 4) of slot p / 4
+  auto dq4 = [&](int p, int r) {
+    return dequant4(wf[p / SPF][r][p % SPF], (wex[p / SPF][r] >> (8 * (p % SPF))) & 0xffu);
+  };
+  auto reload4 = [&](int p, long done) {  // after the slot's last k-step: super-fragment `done` + NSLOT
+    const long qn = min(done + NSLOT, (long)nld - 1);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      wf[p / SPF][r] = __builtin_nontemporal_load(wrow[r] + qn * 64);
+      wex[p / SPF][r] = __builtin_nontemporal_load(wxrow[r] + qn * 16);
+    }
+  };
 
   if constexpr (KIN) {
     // B fragment of k-step s: lane (column m = lane & 15, k = 8 (lane >> 4) ..)
@@ -289,12 +343,17 @@ __global__ __launch_bounds__(256, (MT * KC_ > 32 || R * MT >= 16) ? 1 : 2) void 
         for (int r = 0; r < R; ++r) {
           bf16x8 wdq;
           if constexpr (W8) wdq = dequant8(wf[p][r], wsc[r]);
+          else if constexpr (W4) wdq = dq4(p, r);
           else wdq = wf[p][r];
           acc[r][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wdq, xf[p], acc[r][0], 0, 0, 0);
         }
         const int sn = min(s0 + p + PF, nsteps - 1);
+        if constexpr (W4) {
+          if (p % SPF == SPF - 1) reload4(p, (s0 + p) / SPF);
+        } else {
 #pragma unroll
-        for (int r = 0; r < R; ++r) wf[p][r] = __builtin_nontemporal_load(wrow[r] + (long)sn * 64);
+          for (int r = 0; r < R; ++r) wf[p][r] = __builtin_nontemporal_load(wrow[r] + (long)sn * 64);
+        }
         xf[p] = *(const bf16x8*)(xr + sn * 32);
       }
     }
@@ -330,6 +389,7 @@ __global__ __launch_bounds__(256, (MT * KC_ > 32 || R * MT >= 16) ? 1 : 2) void 
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if constexpr (W8) wdq[r] = dequant8(wf[p][r], wsc[r]);
+        else if constexpr (W4) wdq[r] = dq4(p, r);
         else wdq[r] = wf[p][r];
       }
 #pragma unroll
@@ -340,8 +400,12 @@ __global__ __launch_bounds__(256, (MT * KC_ > 32 || R * MT >= 16) ? 1 : 2) void 
           acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wdq[r], bfrag, acc[r][c], 0, 0, 0);
       }
       const long sn = min(chunk * KC + kk + PF, nsteps - 1);
+      if constexpr (W4) {
+        if (p % SPF == SPF - 1) reload4(p, (long)chunk * (KC / SPF) + kk / SPF);
+      } else {
 #pragma unroll
-      for (int r = 0; r < R; ++r) wf[p][r] = __builtin_nontemporal_load(wrow[r] + sn * 64);
+        for (int r = 0; r < R; ++r) wf[p][r] = __builtin_nontemporal_load(wrow[r] + sn * 64);
+      }
     }
     store_x((chunk + 1) & 1);
     __syncthreads();
@@ -1107,19 +1171,21 @@ constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 int mt_for(int M) { return M <= 16 ? 1 : M <= 32 ? 2 : M <= 64 ? 4 : M <= 128 ? 8 : 16; }
 int default_variant(int mt) { return mt == 1 ? 1 : mt == 2 ? 4 : mt == 4 ? 8 : mt == 8 ? 13 : 17; }
 
-template <int R, int MT, int KC, bool W8, bool KIN = false>
+template <int R, int MT, int KC, int WF, bool KIN = false>
 hipError_t launch_skinny(const void* wp, const void* x, void* y, float* ws, int* cnt, int M, int N, int K, long ldx,
                          long ldy, int ksplit, int cps, const kgs::dec::SkinnyEpi& ep, hipStream_t s) {
   const int nstrip = N / ((KIN ? 16 : 64) * R);
-  if constexpr (!W8 && MT <= 4 && R == 1) {  // the fused layer's qkv variants (kgs/ops/decode.py rope_variant)
+  // the fused layer's qkv variants (kgs/ops/decode.py rope_variant)
+  if constexpr (WF == kgs::dec::WF_BF16 && MT <= 4 && R == 1) {
     if (ep.mode & kgs::dec::EPI_ROPE) {
-      hipLaunchKernelGGL((kgs::dec::skinny<R, MT, KC, false, true, KIN>), dim3(nstrip * ksplit), dim3(256), 0, s, wp,
-                         (const unsigned short*)x, (unsigned short*)y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep);
+      hipLaunchKernelGGL((kgs::dec::skinny<R, MT, KC, kgs::dec::WF_BF16, true, KIN>), dim3(nstrip * ksplit),
+                         dim3(256), 0, s, wp, (const unsigned short*)x, (unsigned short*)y, ws, cnt, M, N, K, ldx, ldy,
+                         ksplit, cps, ep);
       return hipGetLastError();
     }
   }
   if (ep.mode & kgs::dec::EPI_ROPE) return hipErrorInvalidValue;  // no RoPE instantiation for this variant
-  hipLaunchKernelGGL((kgs::dec::skinny<R, MT, KC, W8, false, KIN>), dim3(nstrip * ksplit), dim3(256), 0, s, wp,
+  hipLaunchKernelGGL((kgs::dec::skinny<R, MT, KC, WF, false, KIN>), dim3(nstrip * ksplit), dim3(256), 0, s, wp,
                      (const unsigned short*)x, (unsigned short*)y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep);
   return hipGetLastError();
 }
@@ -1154,7 +1220,8 @@ KGS_EXPORT int kgs_skinny_geometry(int M, int* rows_per_strip, int* k_per_chunk,
 namespace {
 int skinny_fused(const void* wp, const void* x, void* y, float* ws, int* cnt, int M, int N, int K, long ldx, long ldy,
                  int ksplit, int variant, int epi, const float* ss_in, float* ss_out, float* ss_zero, float inv_k,
-                 float eps, const float* wscale, const kgs::dec::SkinnyEpi* rope, hipStream_t s);
+                 float eps, const float* wscale, const kgs::dec::SkinnyEpi* rope, hipStream_t s,
+                 const void* wexp = nullptr);
 }
 
 KGS_EXPORT int kgs_skinny_gemm_bf16_fused(const void* wp, const void* x, void* y, float* ws, int* cnt, int M, int N,
@@ -1164,6 +1231,25 @@ KGS_EXPORT int kgs_skinny_gemm_bf16_fused(const void* wp, const void* x, void* y
   if (epi & kgs::dec::EPI_ROPE) return KGS_ERR_ARG;  // kgs_skinny_gemm_bf16_rope
   return skinny_fused(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, variant, epi, ss_in, ss_out, ss_zero, inv_k, eps,
                       wscale, nullptr, s);
+}
+
+// The same GEMM over MXFP4 weights (W4A16, batches <= 64): `codes` is the e2m1
+// super-fragment stream [N/16][K/128][64][16 B], `scales` the e8m0 dwords
+// [N/16][K/128][16] (kgs/ops/decode.py pack_mxfp4). Everything else as in
+// kgs_skinny_gemm_bf16_fused. Before any launch: K % 128 -> KGS_ERR_SHAPE;
+// null scales, EPI_ROPE, variants 13-19 (or a batch above 64) -> KGS_ERR_ARG;
+// misaligned scales -> KGS_ERR_ALIGN.
+KGS_EXPORT int kgs_skinny_gemm_mxfp4_fused(const void* codes, const void* scales, const void* x, void* y, float* ws,
+                                          int* cnt, int M, int N, int K, long ldx, long ldy, int ksplit, int variant,
+                                          int epi, const float* ss_in, float* ss_out, float* ss_zero, float inv_k,
+                                          float eps, hipStream_t s) {
+  if (epi & kgs::dec::EPI_ROPE) return KGS_ERR_ARG;
+  if (scales == nullptr) return KGS_ERR_ARG;
+  if (!al16(scales)) return KGS_ERR_ALIGN;
+  if (K <= 0 || K % 128) return KGS_ERR_SHAPE;
+  if (M > 64 || (variant > 12 && variant < 20)) return KGS_ERR_ARG;
+  return skinny_fused(codes, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, variant, epi, ss_in, ss_out, ss_zero, inv_k, eps,
+                      nullptr, nullptr, s, scales);
 }
 
 // The fused qkv projection with RoPE + the KV-cache write in its epilogue
@@ -1195,7 +1281,7 @@ KGS_EXPORT int kgs_skinny_gemm_bf16_rope(const void* wp, const void* x, void* y,
 namespace {
 int skinny_fused(const void* wp, const void* x, void* y, float* ws, int* cnt, int M, int N, int K, long ldx, long ldy,
                  int ksplit, int variant, int epi, const float* ss_in, float* ss_out, float* ss_zero, float inv_k,
-                 float eps, const float* wscale, const kgs::dec::SkinnyEpi* rope, hipStream_t s) {
+                 float eps, const float* wscale, const kgs::dec::SkinnyEpi* rope, hipStream_t s, const void* wexp) {
   using namespace kgs::dec;
   int rps, kpc, mpad;
   const int rc = kgs_skinny_variant_geometry(variant, M, &rps, &kpc, &mpad);
@@ -1203,8 +1289,9 @@ int skinny_fused(const void* wp, const void* x, void* y, float* ws, int* cnt, in
   if (variant == 0) variant = default_variant(mt_for(M));
   if (epi & ~(EPI_SWIGLU | EPI_RMS | EPI_RESID | EPI_ROPE) || ((epi & EPI_SWIGLU) && (epi & EPI_RESID)))
     return KGS_ERR_ARG;
-  if ((epi & EPI_ROPE) && (rope == nullptr || (epi & (EPI_SWIGLU | EPI_RESID)) || wscale != nullptr))
+  if ((epi & EPI_ROPE) && (rope == nullptr || (epi & (EPI_SWIGLU | EPI_RESID)) || wscale != nullptr || wexp != nullptr))
     return KGS_ERR_ARG;
+  if (wexp != nullptr && (wscale != nullptr || K % 128)) return KGS_ERR_ARG;
   if (((epi & EPI_RMS) && ss_in == nullptr) || ((epi & EPI_RESID) && ss_out == nullptr)) return KGS_ERR_ARG;
   if (N <= 0 || K <= 0 || N % rps || K % kpc || ldx < K || ldy < ((epi & EPI_SWIGLU) ? N / 2 : N))
     return KGS_ERR_SHAPE;
@@ -1220,15 +1307,20 @@ int skinny_fused(const void* wp, const void* x, void* y, float* ws, int* cnt, in
   ep.ss_zero = ss_zero;
   ep.inv_k = inv_k;
   ep.eps = eps;
-  ep.wscale = wscale;
-  const bool w8 = wscale != nullptr;
-  if (w8 && variant > 12 && variant < 20) return KGS_ERR_ARG;  // fp8 weights: batch buckets <= 64
-  switch (variant * 2 + (w8 ? 1 : 0)) {
+  ep.wscale = wexp != nullptr ? (const float*)wexp : wscale;
+  const int wf = wexp != nullptr ? WF_MXFP4 : wscale != nullptr ? WF_E4M3 : WF_BF16;
+  if (wf != WF_BF16 && variant > 12 && variant < 20) return KGS_ERR_ARG;  // quantised weights: batch buckets <= 64
+  switch (variant * 4 + wf) {
 #define KGS_SKV(id, R, MT, KC)                                                                                       \
-  case 2 * id: return (int)launch_skinny<R, MT, KC, false>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s); \
-  case 2 * id + 1:                                                                                                    \
-    if constexpr (id <= 12) return (int)launch_skinny<R, MT, KC, true>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit,  \
-                                                                        cps, ep, s);                                  \
+  case 4 * id:                                                                                                        \
+    return (int)launch_skinny<R, MT, KC, WF_BF16>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s);          \
+  case 4 * id + 1:                                                                                                    \
+    if constexpr (id <= 12) return (int)launch_skinny<R, MT, KC, WF_E4M3>(wp, x, y, ws, cnt, M, N, K, ldx, ldy,       \
+                                                                           ksplit, cps, ep, s);                       \
+    return KGS_ERR_ARG;                                                                                               \
+  case 4 * id + 2:                                                                                                    \
+    if constexpr (id <= 12) return (int)launch_skinny<R, MT, KC, WF_MXFP4>(wp, x, y, ws, cnt, M, N, K, ldx, ldy,      \
+                                                                            ksplit, cps, ep, s);                      \
     return KGS_ERR_ARG;
     KGS_SKV(1, 1, 1, 16) KGS_SKV(2, 1, 1, 8) KGS_SKV(3, 2, 1, 16)
     KGS_SKV(4, 1, 2, 16) KGS_SKV(5, 1, 2, 8) KGS_SKV(6, 2, 2, 8) KGS_SKV(7, 2, 2, 16)
@@ -1236,10 +1328,12 @@ int skinny_fused(const void* wp, const void* x, void* y, float* ws, int* cnt, in
     KGS_SKV(13, 2, 8, 2) KGS_SKV(14, 2, 8, 4) KGS_SKV(15, 4, 8, 2) KGS_SKV(16, 1, 8, 4)
     KGS_SKV(17, 2, 16, 2) KGS_SKV(18, 1, 16, 4) KGS_SKV(19, 1, 16, 2)
 #undef KGS_SKV
-    case 2 * 20: return (int)launch_skinny<1, 1, 8, false, true>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s);
-    case 2 * 20 + 1: return (int)launch_skinny<1, 1, 8, true, true>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s);
-    case 2 * 21: return (int)launch_skinny<2, 1, 8, false, true>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s);
-    case 2 * 21 + 1: return (int)launch_skinny<2, 1, 8, true, true>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s);
+#define KGS_SKIN(id, R, WF) \
+  case 4 * id + WF:         \
+    return (int)launch_skinny<R, 1, 8, WF, true>(wp, x, y, ws, cnt, M, N, K, ldx, ldy, ksplit, cps, ep, s);
+    KGS_SKIN(20, 1, WF_BF16) KGS_SKIN(20, 1, WF_E4M3) KGS_SKIN(20, 1, WF_MXFP4)
+    KGS_SKIN(21, 2, WF_BF16) KGS_SKIN(21, 2, WF_E4M3) KGS_SKIN(21, 2, WF_MXFP4)
+#undef KGS_SKIN
     default: return KGS_ERR_ARG;
   }
 }
