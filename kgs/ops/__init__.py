@@ -7,6 +7,9 @@
 * :func:`add_rmsnorm`, :func:`rope_qkv_`, :func:`silu_mul`, :func:`attention_qkv` --
   fused decoder-block ops and flash attention (``native/kernels/transformer.hip``,
   ``native/kernels/attention.hip``)
+* :func:`flash_attention_qkv`, :func:`attention_qkv_lse`, :func:`attention_qkv_backward` --
+  differentiable flash attention: forward with log-sum-exp and the dQ / dK / dV
+  kernels (``native/kernels/attention_train.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -21,6 +24,7 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
 
         return getattr(gemm, name)
     if name in ("add_rmsnorm", "rms_norm", "rope_qkv_", "rope_tables", "silu_mul", "attention_qkv",
+                "attention_qkv_lse", "attention_qkv_backward", "flash_attention_qkv",
                 "add_rmsnorm_fp8", "silu_mul_fp8", "quantize_rows_fp8", "argmax_rows", "sample_rows",
                 "sample_rows_reference", "penalize_rows", "token_counts_add", "logprob_rows",
                 "penalize_rows_reference", "logprob_rows_reference"):

@@ -12,6 +12,10 @@ tests compare them with.
   :func:`kgs.ops.gemm.gemm_fp8_rows` (W8A8, per-token dynamic activation scales)
 * :func:`attention_qkv` -- causal/full GQA flash attention (head_dim 128) reading
   q, k, v straight out of the fused QKV buffer and writing ``[tokens, H*128]``
+* :func:`attention_qkv_lse`, :func:`attention_qkv_backward`, :func:`flash_attention_qkv`
+  -- the same attention for training: the forward that keeps the log-sum-exp, the
+  dQ / dK / dV kernels and the autograd op over them
+  (``native/kernels/attention_train.hip``)
 * :func:`paged_prefill_plan`, :func:`paged_prefill_attention` -- every prompt
   chunk of a chunked-prefill step in one launch, keys / values read in place
   from the bf16 KV pages (``native/kernels/attention_paged.hip``)
@@ -572,6 +576,120 @@ def attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads:
     return out
 
 
+def _bf16_rows(t: torch.Tensor, name: str, rows: int, cols: int) -> None:
+    # dtype and shape before the device, so a wrong call fails the same way everywhere
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} must be bf16")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be a row-major 2-D matrix")
+    if t.shape[0] < rows or t.shape[1] < cols:
+        raise ValueError(f"{name} shape does not match batch/seq/heads")
+
+
+def _attn_check(qkv, batch, seq, heads, kv_heads, head_dim):
+    if head_dim != 128:
+        raise ValueError("the training attention kernels take head_dim 128")
+    if heads <= 0 or kv_heads <= 0 or heads % kv_heads:
+        raise ValueError("heads must be a positive multiple of kv_heads")
+    if batch <= 0 or seq <= 0 or seq % 128:
+        raise ValueError("seq must be a positive multiple of 128")
+    _bf16_rows(qkv, "qkv", batch * seq, (heads + 2 * kv_heads) * head_dim)
+    if qkv.shape[0] != batch * seq:
+        raise ValueError("qkv shape does not match batch/seq/heads")
+    _need(qkv, "qkv")
+
+
+def attention_qkv_lse(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads: int, causal: bool = True,
+                      scale: float | None = None, head_dim: int = 128) -> tuple[torch.Tensor, torch.Tensor]:
+    """:func:`attention_qkv` (the same output bits) that also returns each query
+    row's log-sum-exp of the scaled, masked scores: ``lse`` fp32 ``[batch*heads,
+    seq]``, natural log -- what :func:`attention_qkv_backward` recomputes P from."""
+    _attn_check(qkv, batch, seq, heads, kv_heads, head_dim)
+    out = torch.empty((batch * seq, heads * head_dim), dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty((batch * heads, seq), dtype=torch.float32, device=qkv.device)
+    scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
+    ld, esz, base = qkv.stride(0), qkv.element_size(), qkv.data_ptr()
+    rc = _lib.lib().kgs_attn_fwd_lse_bf16(base, base + heads * head_dim * esz,
+                                          base + (heads + kv_heads) * head_dim * esz, out.data_ptr(), lse.data_ptr(),
+                                          batch, seq, heads, kv_heads, head_dim, ld, ld, ld, out.stride(0),
+                                          float(scale), 1 if causal else 0, _lib.stream_handle(qkv.device))
+    _lib.check(rc, "attention_qkv_lse")
+    return out, lse
+
+
+def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, batch: int,
+                           seq: int, heads: int, kv_heads: int, causal: bool = True, scale: float | None = None,
+                           dqkv: torch.Tensor | None = None, head_dim: int = 128, _stages: int = 7) -> torch.Tensor:
+    """Gradients of :func:`attention_qkv_lse` with respect to ``qkv`` from the
+    output's gradient ``dout`` (bf16 ``[batch*seq, >= heads*128]``, any row
+    stride), in the fused layout: ``dqkv`` bf16 ``[batch*seq, >= (heads +
+    2*kv_heads)*128]`` holds dq, dk and dv as its three column groups (only those
+    columns are written), so the QKV projection's backward consumes it with no
+    ``cat``. Three launches (delta, dK/dV, dQ), no atomics: bitwise reproducible."""
+    t, qc, w = batch * seq, heads * head_dim, (heads + 2 * kv_heads) * head_dim
+    for x, n in ((out, "out"), (dout, "dout")):
+        _bf16_rows(x, n, t, qc)
+        if x.shape[0] != t:
+            raise ValueError(f"{n} shape does not match batch/seq/heads")
+    if lse.dtype != torch.float32:
+        raise TypeError("lse must be fp32")
+    if lse.shape != (batch * heads, seq) or not lse.is_contiguous():
+        raise ValueError("lse must be contiguous [batch*heads, seq]")
+    if dqkv is not None:
+        _bf16_rows(dqkv, "dqkv", t, w)
+    _attn_check(qkv, batch, seq, heads, kv_heads, head_dim)
+    for x, n in ((out, "out"), (dout, "dout"), (lse, "lse")) + (((dqkv, "dqkv"),) if dqkv is not None else ()):
+        if not x.is_cuda:
+            raise ValueError(f"{n} must be on a GPU")
+    if dqkv is None:
+        dqkv = torch.empty((t, w), dtype=torch.bfloat16, device=qkv.device)
+    ws = torch.empty((batch * heads, seq), dtype=torch.float32, device=qkv.device)
+    scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
+    ld, esz, base = qkv.stride(0), qkv.element_size(), qkv.data_ptr()
+    dld, dbase = dqkv.stride(0), dqkv.data_ptr()
+    ko, vo = heads * head_dim * esz, (heads + kv_heads) * head_dim * esz
+    rc = _lib.lib().kgs_attn_bwd_bf16_ex(base, base + ko, base + vo, out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                         dbase, dbase + ko, dbase + vo, ws.data_ptr(), batch, seq, heads, kv_heads,
+                                         head_dim, ld, ld, ld, out.stride(0), dout.stride(0), dld, dld, dld,
+                                         float(scale), 1 if causal else 0, int(_stages),
+                                         _lib.stream_handle(qkv.device))
+    _lib.check(rc, "attention_qkv_backward")
+    return dqkv
+
+
+class _FlashAttnFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, batch, seq, heads, kv_heads, causal, scale):
+        if not ctx.needs_input_grad[0]:
+            return attention_qkv(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale)  # inference: unchanged
+        out, lse = attention_qkv_lse(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.cfg = (batch, seq, heads, kv_heads, causal, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        batch, seq, heads, kv_heads, causal, scale = ctx.cfg
+        if dout.stride(1) != 1:
+            dout = dout.contiguous()
+        dqkv = attention_qkv_backward(qkv, out, dout, lse, batch, seq, heads, kv_heads, causal=causal, scale=scale)
+        if qkv.shape[1] != dqkv.shape[1]:  # a qkv wider than its three groups: the rest has no gradient
+            full = torch.zeros_like(qkv)
+            full[:, :dqkv.shape[1]] = dqkv
+            dqkv = full
+        return dqkv, None, None, None, None, None, None
+
+
+def flash_attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads: int, causal: bool = True,
+                        scale: float | None = None) -> torch.Tensor:
+    """Differentiable :func:`attention_qkv` (head_dim 128, ``seq % 128 == 0``):
+    forward and backward on the HIP kernels. When ``qkv`` needs no gradient this
+    IS :func:`attention_qkv` (nothing saved)."""
+    _attn_check(qkv, batch, seq, heads, kv_heads, 128)
+    return _FlashAttnFn.apply(qkv, batch, seq, heads, kv_heads, causal, scale)
+
+
 def attention_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int,
                     head_dim: int = 128, scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Causal flash attention of one sequence's prefill CHUNK over its whole
@@ -776,3 +894,15 @@ def ref_attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=128, causal=Tru
     v = v.transpose(1, 2).repeat_interleave(rep, dim=1)
     o = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale)
     return o.transpose(1, 2).reshape(t, heads * head_dim)
+
+
+def ref_attention_qkv_backward(qkv, dout, batch, seq, heads, kv_heads, head_dim=128, causal=True, scale=None):
+    """fp32 reference of :func:`attention_qkv_backward` (CPU or GPU tensors):
+    autograd through :func:`ref_attention_qkv` on an fp32 leaf. Returns the fp32
+    gradient in the fused layout ``[batch*seq, (heads + 2*kv_heads) * head_dim]``."""
+    w = (heads + 2 * kv_heads) * head_dim
+    leaf = qkv[:, :w].detach().float().clone().requires_grad_(True)
+    with torch.enable_grad():
+        o = ref_attention_qkv(leaf, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale)
+    (g,) = torch.autograd.grad(o, leaf, dout[:, :heads * head_dim].detach().to(o.dtype))
+    return g
