@@ -10,6 +10,10 @@
 * :func:`flash_attention_qkv`, :func:`attention_qkv_lse`, :func:`attention_qkv_backward` --
   differentiable flash attention: forward with log-sum-exp and the dQ / dK / dV
   kernels (``native/kernels/attention_train.hip``)
+* :func:`rmsnorm_residual`, :func:`swiglu`, :func:`rope_qkv`, :func:`softmax_cross_entropy` --
+  the differentiable norm, SwiGLU, RoPE and LM loss, over :func:`rmsnorm_backward`,
+  :func:`silu_mul_backward`, :func:`cross_entropy_rows` and
+  :func:`cross_entropy_rows_backward` (``native/kernels/train_ops.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -25,6 +29,8 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         return getattr(gemm, name)
     if name in ("add_rmsnorm", "rms_norm", "rope_qkv_", "rope_tables", "silu_mul", "attention_qkv",
                 "attention_qkv_lse", "attention_qkv_backward", "flash_attention_qkv",
+                "rmsnorm_backward", "silu_mul_backward", "cross_entropy_rows", "cross_entropy_rows_backward",
+                "rmsnorm_residual", "swiglu", "rope_qkv", "softmax_cross_entropy",
                 "add_rmsnorm_fp8", "silu_mul_fp8", "quantize_rows_fp8", "argmax_rows", "sample_rows",
                 "sample_rows_reference", "penalize_rows", "token_counts_add", "logprob_rows",
                 "penalize_rows_reference", "logprob_rows_reference"):

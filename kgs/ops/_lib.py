@@ -83,6 +83,12 @@ _SIGS = {
                           _c_int),
     "kgs_attn_bwd_bf16_ex": ([_c_void_p] * 10 + [_c_int] * 5 + [_c_long] * 8 + [ctypes.c_float, _c_int, _c_int,
                                                                                  _c_void_p], _c_int),
+    # training glue (native/kernels/train_ops.hip)
+    "kgs_rmsnorm_bwd_workspace": ([_c_int, _c_int], _c_long),
+    "kgs_rmsnorm_bwd_bf16": ([_c_void_p] * 7 + [_c_int, _c_int] + [_c_long] * 4 + [ctypes.c_float, _c_void_p], _c_int),
+    "kgs_silu_mul_bwd_bf16": ([_c_void_p] * 3 + [_c_long, _c_int] + [_c_long] * 3 + [_c_void_p], _c_int),
+    "kgs_xent_fwd_bf16": ([_c_void_p] * 4 + [_c_int, _c_int, _c_long, _c_void_p], _c_int),
+    "kgs_xent_bwd_bf16": ([_c_void_p] * 5 + [_c_int, _c_int, _c_long, _c_long, _c_void_p], _c_int),
     # paged prefill attention (native/kernels/attention_paged.hip)
     "kgs_attn_prefill_paged_bf16": ([_c_void_p] * 6 + [_c_int] * 6 + [_c_long] * 2 + [ctypes.c_float, _c_void_p],
                                     _c_int),

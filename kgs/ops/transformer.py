@@ -16,6 +16,11 @@ tests compare them with.
   -- the same attention for training: the forward that keeps the log-sum-exp, the
   dQ / dK / dV kernels and the autograd op over them
   (``native/kernels/attention_train.hip``)
+* :func:`rmsnorm_backward`, :func:`silu_mul_backward`, :func:`cross_entropy_rows`,
+  :func:`cross_entropy_rows_backward` -- the backward kernels of the norm and of
+  SwiGLU and the softmax cross-entropy over logit rows
+  (``native/kernels/train_ops.hip``); :func:`rmsnorm_residual`, :func:`swiglu`,
+  :func:`rope_qkv`, :func:`softmax_cross_entropy` -- the autograd ops over them
 * :func:`paged_prefill_plan`, :func:`paged_prefill_attention` -- every prompt
   chunk of a chunked-prefill step in one launch, keys / values read in place
   from the bf16 KV pages (``native/kernels/attention_paged.hip``)
@@ -690,6 +695,303 @@ def flash_attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_
     return _FlashAttnFn.apply(qkv, batch, seq, heads, kv_heads, causal, scale)
 
 
+# ----------------------------------------------------------------------------
+# training glue (native/kernels/train_ops.hip): raw backward ops, then the autograd ops
+
+def _bf16_matrix(t: torch.Tensor, name: str, shape: tuple | None = None) -> None:
+    # dtype and shape before the device, so a wrong call fails the same way everywhere
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} must be a bf16 tensor")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be a row-major 2-D matrix")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _on_gpu(*named) -> None:
+    dev = None
+    for t, name in named:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be on a GPU")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{name} must be on the device of the other operands")
+        dev = t.device
+
+
+def rmsnorm_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, dres: torch.Tensor | None = None,
+                     eps: float = 1e-5) -> tuple[torch.Tensor, torch.Tensor]:
+    """Gradients of ``y = rmsnorm(x) * w`` (the norm half of :func:`add_rmsnorm`):
+    ``(dx, dw)``, bf16 ``[rows, cols]`` and ``[cols]``. ``x`` is the stream value the
+    forward normalised (``x + d`` as it wrote it back), ``dy`` the gradient of ``y``
+    and ``dres``, when given, the gradient that reaches the same stream value
+    through the residual branch: it is added in fp32, before dx's one rounding.
+    Per row ``r = rsqrt(mean(x^2) + eps)`` is recomputed, ``g = dy * w``, ``c =
+    sum(g * x) / cols``, ``dx = dres + r g - x r^3 c``; ``dw = sum_rows dy x r``.
+    Any row strides (multiples of 8); cols a multiple of 512 up to 8192. Two
+    launches, no atomics: bitwise reproducible."""
+    _bf16_matrix(x, "x")
+    rows, cols = x.shape
+    if cols % 512 or not 0 < cols <= 8192:
+        raise ValueError("cols must be a multiple of 512 up to 8192")
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.bfloat16:
+        raise TypeError("w must be a bf16 tensor")
+    if w.shape != (cols,) or not w.is_contiguous():
+        raise ValueError("w must be a contiguous bf16 vector of length cols")
+    _bf16_matrix(dy, "dy", (rows, cols))
+    if dres is not None:
+        _bf16_matrix(dres, "dres", (rows, cols))
+    _on_gpu((x, "x"), (w, "w"), (dy, "dy"), (dres, "dres"))
+    dx = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
+    dw = torch.empty(cols, dtype=torch.bfloat16, device=x.device)
+    lib = _lib.lib()
+    ws = torch.empty(lib.kgs_rmsnorm_bwd_workspace(rows, cols) // 4, dtype=torch.float32, device=x.device)
+    rc = lib.kgs_rmsnorm_bwd_bf16(x.data_ptr(), w.data_ptr(), dy.data_ptr(), 0 if dres is None else dres.data_ptr(),
+                                  dx.data_ptr(), dw.data_ptr(), ws.data_ptr(), rows, cols, x.stride(0), dy.stride(0),
+                                  0 if dres is None else dres.stride(0), dx.stride(0), float(eps),
+                                  _lib.stream_handle(x.device))
+    _lib.check(rc, "rmsnorm_backward")
+    return dx, dw
+
+
+def silu_mul_backward(gu: torch.Tensor, dh: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Gradient of :func:`silu_mul` with respect to the fused gate|up input:
+    ``dgu`` bf16 ``[rows, 2I]`` (dgate | dup, the layout the gate/up projection's
+    backward consumes with no ``cat``) from ``gu`` ``[rows, 2I]`` and ``dh`` ``[rows, I]``.
+    With ``s = sigmoid(g)``: ``dgate = dh u s (1 + g (1 - s))``, ``dup = dh g s``.
+    Any row strides (multiples of 8); ``I % 8 == 0``."""
+    _bf16_matrix(gu, "gu")
+    rows, w2 = gu.shape
+    if w2 % 16 or w2 == 0:
+        raise ValueError("gu must be [rows, 2I] with I a positive multiple of 8")
+    inter = w2 // 2
+    _bf16_matrix(dh, "dh", (rows, inter))
+    if out is not None:
+        _bf16_matrix(out, "out", (rows, w2))
+    _on_gpu((gu, "gu"), (dh, "dh"), (out, "out"))
+    if out is None:
+        out = torch.empty((rows, w2), dtype=torch.bfloat16, device=gu.device)
+    rc = _lib.lib().kgs_silu_mul_bwd_bf16(gu.data_ptr(), dh.data_ptr(), out.data_ptr(), rows, inter, gu.stride(0),
+                                          dh.stride(0), out.stride(0), _lib.stream_handle(gu.device))
+    _lib.check(rc, "silu_mul_backward")
+    return out
+
+
+def _xent_check(logits, target):
+    _bf16_matrix(logits, "logits")
+    rows, cols = logits.shape
+    if cols % 8 or cols == 0:
+        raise ValueError("logits must have a positive multiple of 8 columns")
+    _typed([("target", torch.int64, target)])
+    _row_vectors([("target", None, target)], rows)
+    return rows, cols
+
+
+def cross_entropy_rows(logits: torch.Tensor, target: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Softmax cross-entropy of every row of bf16 GPU logits ``[rows, cols]`` (cols % 8
+    == 0, any row stride) in one pass: ``(loss, lse)``, fp32 ``[rows]``. ``lse`` is the
+    row's log-sum-exp (natural log) and ``loss = lse - logits[row, target[row]]``. A
+    target outside ``[0, cols)`` (``ignore_index = -100``) makes the row ignored:
+    its loss is 0, its lse is still written."""
+    rows, cols = _xent_check(logits, target)
+    _on_gpu((logits, "logits"), (target, "target"))
+    loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    rc = _lib.lib().kgs_xent_fwd_bf16(logits.data_ptr(), target.data_ptr(), loss.data_ptr(), lse.data_ptr(), rows,
+                                      cols, logits.stride(0), _lib.stream_handle(logits.device))
+    _lib.check(rc, "cross_entropy_rows")
+    return loss, lse
+
+
+def cross_entropy_rows_backward(logits: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, grow: torch.Tensor,
+                                out: torch.Tensor | None = None) -> torch.Tensor:
+    """Gradient of :func:`cross_entropy_rows`' loss with respect to the logits:
+    ``dlogits[row, j] = bf16(grow[row] * (exp(logits[row, j] - lse[row]) - [j ==
+    target[row]]))``, ``grow`` the fp32 gradient of each row's loss. At the target
+    column ``p - 1`` is evaluated as minus the sum of the other columns' ``p``, which
+    does not cancel when ``p`` is 1 in fp32. An ignored row is written as zeros.
+    ``out``: a bf16 ``[rows, cols]`` buffer of its own (any row stride); only its
+    columns ``< cols`` are written."""
+    rows, cols = _xent_check(logits, target)
+    vecs = [("lse", torch.float32, lse), ("grow", torch.float32, grow)]
+    _typed(vecs)
+    _row_vectors(vecs, rows)
+    if out is not None:
+        _bf16_matrix(out, "out", (rows, cols))
+    _on_gpu((logits, "logits"), (target, "target"), (lse, "lse"), (grow, "grow"), (out, "out"))
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.bfloat16, device=logits.device)
+    rc = _lib.lib().kgs_xent_bwd_bf16(logits.data_ptr(), target.data_ptr(), lse.data_ptr(), grow.data_ptr(),
+                                      out.data_ptr(), rows, cols, logits.stride(0), out.stride(0),
+                                      _lib.stream_handle(logits.device))
+    _lib.check(rc, "cross_entropy_rows_backward")
+    return out
+
+
+def _add_rmsnorm_out_of_place(x, d, w, eps):
+    """``(bf16(x + d), rmsnorm(x + d) * w)`` on kgs_add_rmsnorm_bf16 with its separate
+    ``xo`` pointer: ``x`` is left alone."""
+    rows, cols = x.shape
+    res = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
+    y = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
+    if d.stride(0) != cols or x.stride(0) != cols:  # one row stride serves x, d and xo
+        x, d = x.contiguous(), d.contiguous()
+    rc = _lib.lib().kgs_add_rmsnorm_bf16(x.data_ptr(), d.data_ptr(), res.data_ptr(), w.data_ptr(), y.data_ptr(), rows,
+                                         cols, cols, cols, float(eps), _lib.stream_handle(x.device))
+    _lib.check(rc, "rmsnorm_residual")
+    return res, y
+
+
+def _grad_rows(g: torch.Tensor) -> torch.Tensor:
+    """An incoming gradient as the kernels take it: unit column stride, a row stride
+    that is a multiple of 8, 16-byte aligned (autograd may hand over expanded views)."""
+    ok = g.dim() == 2 and g.stride(1) == 1 and g.stride(0) >= g.shape[1] and g.stride(0) % 8 == 0 and \
+        g.data_ptr() % 16 == 0
+    return g if ok else g.contiguous()
+
+
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+class _RmsNormResidualFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, d, w, eps):
+        if d is None:
+            res, y = x, add_rmsnorm(x, None, w, eps)
+        else:
+            res, y = _add_rmsnorm_out_of_place(x, d, w, eps)
+        ctx.save_for_backward(res, w)
+        ctx.eps, ctx.has_d = eps, d is not None
+        return res, y
+
+    @staticmethod
+    def backward(ctx, dres, dy):
+        res, w = ctx.saved_tensors
+        dy = torch.zeros_like(res) if dy is None else _grad_rows(dy)
+        dx, dw = rmsnorm_backward(res, w, dy, None if dres is None else _grad_rows(dres), ctx.eps)
+        return dx, (dx if ctx.has_d else None), dw, None
+
+
+def rmsnorm_residual(x: torch.Tensor, d: torch.Tensor | None, w: torch.Tensor, eps: float = 1e-5
+                     ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Differentiable, out-of-place :func:`add_rmsnorm`: ``(res, y)`` with ``res =
+    bf16(x + d)`` (``x`` itself when ``d`` is None) and ``y = rmsnorm(res) * w``; ``x``
+    and ``d`` are left alone. It saves ``res`` and ``w``; its backward takes ``(dres,
+    dy)`` and makes ONE :func:`rmsnorm_backward` call, whose ``dx`` is the gradient
+    of both ``x`` and ``d`` (the same tensor). With no gradient wanted it is the
+    inference kernel alone, nothing saved."""
+    _bf16_matrix(x, "x")
+    rows, cols = x.shape
+    if cols % 512 or not 0 < cols <= 8192:
+        raise ValueError("cols must be a multiple of 512 up to 8192")
+    if d is not None:
+        _bf16_matrix(d, "d", (rows, cols))
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.bfloat16:
+        raise TypeError("w must be a bf16 tensor")
+    if w.shape != (cols,) or not w.is_contiguous():
+        raise ValueError("w must be a contiguous bf16 vector of length cols")
+    _on_gpu((x, "x"), (d, "d"), (w, "w"))
+    if _wants_grad(x, d, w):
+        return _RmsNormResidualFn.apply(x, d, w, eps)
+    if d is None:
+        return x, add_rmsnorm(x, None, w, eps)
+    return _add_rmsnorm_out_of_place(x, d, w, eps)
+
+
+class _SwiGluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gu):
+        ctx.save_for_backward(gu)
+        return silu_mul(gu)
+
+    @staticmethod
+    def backward(ctx, dh):
+        (gu,) = ctx.saved_tensors
+        return silu_mul_backward(gu, _grad_rows(dh))
+
+
+def swiglu(gu: torch.Tensor) -> torch.Tensor:
+    """Differentiable :func:`silu_mul`: ``silu(gu[:, :I]) * gu[:, I:]``; the backward is
+    :func:`silu_mul_backward` on the saved ``gu``. With no gradient wanted this IS
+    :func:`silu_mul` (nothing saved)."""
+    _bf16_matrix(gu, "gu")
+    if gu.shape[1] % 16 or gu.shape[1] == 0:
+        raise ValueError("gu must be [rows, 2I] with I a positive multiple of 8")
+    _on_gpu((gu, "gu"))
+    return _SwiGluFn.apply(gu) if _wants_grad(gu) else silu_mul(gu)
+
+
+class _RopeQkvFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, heads, head_dim, seq):
+        ctx.save_for_backward(cos, sin)
+        ctx.cfg = (heads, head_dim, seq)
+        if qkv.is_leaf or qkv._base is not None:  # autograd forbids (a leaf) or restricts (a view) the in-place form
+            return rope_qkv_(qkv.clone(memory_format=torch.contiguous_format), cos, sin, heads, head_dim, seq)
+        ctx.mark_dirty(qkv)
+        return rope_qkv_(qkv, cos, sin, heads, head_dim, seq)
+
+    @staticmethod
+    def backward(ctx, dout):
+        cos, sin = ctx.saved_tensors
+        heads, head_dim, seq = ctx.cfg
+        # the transposed rotation is the rotation by -angle; on a private copy: autograd may share dout
+        g = dout.clone(memory_format=torch.contiguous_format)
+        return rope_qkv_(g, cos, -sin, heads, head_dim, seq), None, None, None, None, None
+
+
+def rope_qkv(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, head_dim: int, seq: int
+             ) -> torch.Tensor:
+    """Differentiable :func:`rope_qkv_` (positions ``token % seq`` only): returns the
+    rotated rows. With no gradient wanted this IS :func:`rope_qkv_`, in place. When
+    ``qkv`` needs a gradient the rotation is in place too where autograd allows it (a
+    non-leaf that is not a view: ``qkv`` itself is returned, marked dirty), otherwise
+    on a copy. The backward is the same kernel with the negated ``sin`` table -- the
+    transposed rotation -- on a private copy of the incoming gradient, which is
+    never touched; columns past the rotated heads pass through unchanged."""
+    _bf16_matrix(qkv, "qkv")
+    if head_dim <= 0 or head_dim % 16 or heads <= 0 or seq <= 0:
+        raise ValueError("heads and seq must be positive and head_dim a positive multiple of 16")
+    if qkv.shape[1] < heads * head_dim:
+        raise ValueError("qkv rows must hold heads * head_dim rotated elements")
+    for t, n in ((cos, "cos"), (sin, "sin")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{n} must be an fp32 tensor")
+        if t.dim() != 2 or t.shape[0] < seq or t.shape[1] != head_dim // 2 or not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous fp32 [>= seq, head_dim/2]")
+    _on_gpu((qkv, "qkv"), (cos, "cos"), (sin, "sin"))
+    if not _wants_grad(qkv):
+        return rope_qkv_(qkv, cos, sin, heads, head_dim, seq)
+    return _RopeQkvFn.apply(qkv, cos, sin, heads, head_dim, seq)
+
+
+class _SoftmaxXentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        loss, lse = cross_entropy_rows(logits, target)
+        ctx.save_for_backward(logits, target, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grow):
+        logits, target, lse = ctx.saved_tensors
+        return cross_entropy_rows_backward(logits, target, lse, grow.float().contiguous()), None
+
+
+def softmax_cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """Differentiable :func:`cross_entropy_rows`: the fp32 per-row loss ``[rows]`` (0 for
+    ignored rows; the caller takes the mean over the others in torch). It saves
+    ``logits``, ``target`` and the rows' log-sum-exp; the backward is
+    :func:`cross_entropy_rows_backward`. With no gradient wanted nothing is saved."""
+    _xent_check(logits, target)
+    _on_gpu((logits, "logits"), (target, "target"))
+    if not _wants_grad(logits):
+        return cross_entropy_rows(logits, target)[0]
+    return _SoftmaxXentFn.apply(logits, target)
+
+
 def attention_chunk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int,
                     head_dim: int = 128, scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Causal flash attention of one sequence's prefill CHUNK over its whole
@@ -906,3 +1208,61 @@ def ref_attention_qkv_backward(qkv, dout, batch, seq, heads, kv_heads, head_dim=
         o = ref_attention_qkv(leaf, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale)
     (g,) = torch.autograd.grad(o, leaf, dout[:, :heads * head_dim].detach().to(o.dtype))
     return g
+
+
+# ----------------------------------------------------------------------------
+# references of the training glue: the formulas stated directly (not through
+# autograd, which the CPU tests compare them with), fp64 unless asked otherwise
+
+def ref_rmsnorm_backward(x, w, dy, dres=None, eps=1e-5, dtype=torch.float64):
+    """``(dx, dw)`` of :func:`rmsnorm_backward` in ``dtype``, unrounded."""
+    xf, wf, gy = x.to(dtype), w.to(dtype), dy.to(dtype)
+    cols = xf.shape[-1]
+    r = torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    g = gy * wf
+    c = (g * xf).sum(-1, keepdim=True) / cols
+    dx = r * g - xf * r.pow(3) * c
+    if dres is not None:
+        dx = dres.to(dtype) + dx
+    return dx, (gy * xf * r).sum(0)
+
+
+def ref_silu_mul_backward(gu, dh, dtype=torch.float64):
+    """``dgu`` (dgate | dup) of :func:`silu_mul_backward` in ``dtype``, unrounded."""
+    i = gu.shape[1] // 2
+    g, u, d = gu[:, :i].to(dtype), gu[:, i:].to(dtype), dh.to(dtype)
+    s = torch.sigmoid(g)
+    return torch.cat((d * u * s * (1 + g * (1 - s)), d * g * s), dim=1)
+
+
+def ref_rope_qkv_backward(dout, cos, sin, heads, head_dim, seq, dtype=torch.float64):
+    """Gradient of :func:`rope_qkv` in ``dtype``, unrounded: the transposed rotation
+    ``(g1 c + g2 s, g2 c - g1 s)`` on the rotated heads, ``dout`` itself elsewhere."""
+    t = dout.shape[0]
+    g = dout[:, :heads * head_dim].to(dtype).reshape(t, heads, head_dim)
+    pos = torch.arange(t, device=dout.device) % seq
+    c, s = cos[pos][:, None, :].to(dtype), sin[pos][:, None, :].to(dtype)
+    g1, g2 = g[..., :head_dim // 2], g[..., head_dim // 2:]
+    rot = torch.cat((g1 * c + g2 * s, g2 * c - g1 * s), dim=-1).reshape(t, heads * head_dim)
+    return torch.cat((rot, dout[:, heads * head_dim:].to(dtype)), dim=1)
+
+
+def ref_cross_entropy_rows(logits, target, dtype=torch.float64):
+    """``(loss, lse)`` of :func:`cross_entropy_rows` in ``dtype``."""
+    x = logits.to(dtype)
+    cols = x.shape[1]
+    m = x.max(dim=1, keepdim=True).values
+    lse = (m + (x - m).exp().sum(dim=1, keepdim=True).log())[:, 0]
+    live = (target >= 0) & (target < cols)
+    xt = x.gather(1, target.clamp(0, cols - 1)[:, None])[:, 0]
+    return torch.where(live, lse - xt, torch.zeros_like(lse)), lse
+
+
+def ref_cross_entropy_rows_backward(logits, target, lse, grow, dtype=torch.float64):
+    """``dlogits`` of :func:`cross_entropy_rows_backward` in ``dtype``, unrounded."""
+    x = logits.to(dtype)
+    cols = x.shape[1]
+    live = (target >= 0) & (target < cols)
+    onehot = torch.arange(cols, device=x.device)[None, :] == target[:, None]
+    d = grow.to(dtype)[:, None] * ((x - lse.to(dtype)[:, None]).exp() - onehot.to(dtype))
+    return torch.where(live[:, None], d, torch.zeros_like(d))
