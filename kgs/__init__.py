@@ -11,6 +11,7 @@ Subpackages:
   kgs.deviceplugin          kubelet v1beta1 gRPC device plugin
   kgs.gpuinfo               native GPU/xGMI enumeration core (C++)
   kgs.ops                   HIP kernels (GEMM, vector add, ...)
+  kgs.optim                 AdamW with fp32 master weights on the fused optimizer kernels
   kgs.parallel              RCCL collectives via torch.distributed
   kgs.models                the in-pod workload models (GEMM step, MLP)
   kgs.workload              the rocm-gpu-test pod entrypoint

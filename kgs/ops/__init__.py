@@ -14,6 +14,9 @@
   the differentiable norm, SwiGLU, RoPE and LM loss, over :func:`rmsnorm_backward`,
   :func:`silu_mul_backward`, :func:`cross_entropy_rows` and
   :func:`cross_entropy_rows_backward` (``native/kernels/train_ops.hip``)
+* :func:`adamw_table`, :func:`grad_norm`, :func:`adamw_step_` -- the fused AdamW step
+  of every tensor of a model over a device-resident tensor table
+  (``native/kernels/optimizer.hip``); the optimizer on them is :class:`kgs.optim.AdamW`
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -41,4 +44,9 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         from . import elementwise
 
         return getattr(elementwise, name)
+    if name in ("adamw_table", "adamw_step_", "grad_norm", "adamw_chunk", "ref_adamw_step", "ref_grad_norm",
+                "ref_clip"):
+        from . import optim
+
+        return getattr(optim, name)
     raise AttributeError(name)

@@ -89,6 +89,19 @@ _SIGS = {
     "kgs_silu_mul_bwd_bf16": ([_c_void_p] * 3 + [_c_long, _c_int] + [_c_long] * 3 + [_c_void_p], _c_int),
     "kgs_xent_fwd_bf16": ([_c_void_p] * 4 + [_c_int, _c_int, _c_long, _c_void_p], _c_int),
     "kgs_xent_bwd_bf16": ([_c_void_p] * 5 + [_c_int, _c_int, _c_long, _c_long, _c_void_p], _c_int),
+    # fused AdamW (native/kernels/optimizer.hip)
+    "kgs_adamw_chunk": ([], _c_int),
+    "kgs_adamw_row_bytes": ([], _c_int),
+    "kgs_adamw_state_bytes": ([], _c_int),
+    "kgs_adamw_step_default_variant": ([], _c_int),
+    "kgs_adamw_sumsq_default_variant": ([], _c_int),
+    "kgs_adamw_table_check": ([_c_void_p, _c_int, _c_int], _c_long),
+    "kgs_adamw_grad_sumsq": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p], _c_int),
+    "kgs_adamw_grad_sumsq_v": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_int, _c_void_p], _c_int),
+    "kgs_adamw_finalize": ([_c_void_p, _c_long] + [ctypes.c_float] * 3 + [_c_void_p, _c_void_p], _c_int),
+    "kgs_adamw_step": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p] + [ctypes.c_float] * 3 + [_c_void_p], _c_int),
+    "kgs_adamw_step_v": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p] + [ctypes.c_float] * 3 +
+                         [_c_int, _c_void_p], _c_int),
     # paged prefill attention (native/kernels/attention_paged.hip)
     "kgs_attn_prefill_paged_bf16": ([_c_void_p] * 6 + [_c_int] * 6 + [_c_long] * 2 + [ctypes.c_float, _c_void_p],
                                     _c_int),
