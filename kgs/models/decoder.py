@@ -20,7 +20,11 @@ torch autograd ops: the layer as it could be built before those kernels, kept fo
 the benchmark's comparison. ``backend="torch"`` is the same module on
 ``nn.Linear``, ``scaled_dot_product_attention`` and torch glue (CPU tests, the
 fp32 reference copy, the PyTorch-ROCm comparison). Both backends start from the
-same seeded weights. The reference has no model code; nothing here is ported.
+same seeded weights. ``linear="fp8"`` swaps the four projections (qkv, o, gate|up,
+down) for :class:`kgs.ops.LinearFp8` -- forward, dX and dW in e4m3 -- or, with
+``backend="torch"``, for its torch model :class:`kgs.ops.RefLinearFp8`; the LM
+head and the embedding stay as they are. The reference has no model code;
+nothing here is ported.
 """
 from __future__ import annotations
 
@@ -44,16 +48,18 @@ def _torch_swiglu(gu: torch.Tensor) -> torch.Tensor:
 class DecoderLayer(torch.nn.Module):
     def __init__(self, dim: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs", glue: str | None = None,
                  causal: bool = True, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
-                 dtype=torch.bfloat16, seed: int = 0):
+                 dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16"):
         super().__init__()
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', not {backend!r}")
+        if linear not in ("bf16", "fp8"):
+            raise ValueError(f"linear must be 'bf16' or 'fp8', not {linear!r}")
         glue = backend if glue is None else glue
         if glue not in ("kgs", "torch") or (backend == "torch" and glue == "kgs"):
             raise ValueError("glue must be 'kgs' (with the kgs backend only) or 'torch'")
         if dim % heads or heads % kv_heads:
             raise ValueError("dim must divide by heads and heads by kv_heads")
-        self.backend, self.glue, self.dim, self.inter = backend, glue, dim, inter
+        self.backend, self.glue, self.dim, self.inter, self.linear = backend, glue, dim, inter, linear
         self.heads, self.kv_heads = heads, kv_heads
         self.head_dim, self.causal, self.rope_theta, self.eps = dim // heads, causal, rope_theta, eps
         if backend == "kgs" and (self.head_dim != 128 or dtype != torch.bfloat16):
@@ -61,7 +67,17 @@ class DecoderLayer(torch.nn.Module):
         if glue == "kgs" and (dim % 512 or dim > 8192 or inter % 8):
             raise ValueError("the kgs glue takes dim a multiple of 512 up to 8192 and inter a multiple of 8")
         wqkv = (heads + 2 * kv_heads) * self.head_dim
-        if backend == "kgs":
+        if linear == "fp8" and backend == "kgs":
+            from kgs.ops.fp8_train import LinearFp8
+
+            def lin(i, o):
+                return LinearFp8(i, o, bias=False, device=device)
+        elif linear == "fp8":
+            from kgs.ops.fp8_train import RefLinearFp8
+
+            def lin(i, o):
+                return RefLinearFp8(i, o, bias=False, device=device, dtype=dtype)
+        elif backend == "kgs":
             from kgs.ops.gemm import Linear
 
             def lin(i, o):
@@ -130,12 +146,14 @@ class DecoderLM(torch.nn.Module):
 
     def __init__(self, vocab: int, dim: int, layers: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs",
                  glue: str | None = None, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
-                 dtype=torch.bfloat16, seed: int = 0):
+                 dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16"):
         super().__init__()
-        self.vocab, self.dim, self.eps = vocab, dim, eps
+        if linear not in ("bf16", "fp8"):
+            raise ValueError(f"linear must be 'bf16' or 'fp8', not {linear!r}")
+        self.vocab, self.dim, self.eps, self.linear = vocab, dim, eps, linear
         self.layers = torch.nn.ModuleList(
             DecoderLayer(dim, heads, kv_heads, inter, backend=backend, glue=glue, rope_theta=rope_theta, eps=eps,
-                         device=device, dtype=dtype, seed=seed + 1 + i) for i in range(layers))
+                         device=device, dtype=dtype, seed=seed + 1 + i, linear=linear) for i in range(layers))
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:
             raise ValueError("the kgs loss takes a vocabulary that is a multiple of 8")

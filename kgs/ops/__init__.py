@@ -17,6 +17,8 @@
 * :func:`adamw_table`, :func:`grad_norm`, :func:`adamw_step_` -- the fused AdamW step
   of every tensor of a model over a device-resident tensor table
   (``native/kernels/optimizer.hip``); the optimizer on them is :class:`kgs.optim.AdamW`
+* :func:`linear_fp8`, :class:`LinearFp8`, :func:`fp8_amax`, :func:`fp8_quantize`, :func:`ref_linear_fp8` --
+  a trainable Linear whose forward, dX and dW GEMMs run in e4m3 (``native/kernels/fp8_train.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -49,4 +51,8 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         from . import optim
 
         return getattr(optim, name)
+    if name in ("fp8_amax", "fp8_quantize", "linear_fp8", "LinearFp8", "ref_linear_fp8", "RefLinearFp8"):
+        from . import fp8_train
+
+        return getattr(fp8_train, name)
     raise AttributeError(name)
