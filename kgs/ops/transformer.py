@@ -531,8 +531,12 @@ def rope_tables(seq: int, head_dim: int, theta: float, device) -> tuple[torch.Te
 def rope_qkv_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, head_dim: int, seq: int,
               positions: torch.Tensor | None = None) -> torch.Tensor:
     """Rotate (in place) the first ``heads`` heads of every token row of ``qkv``
-    (q heads then k heads). Positions are ``token % seq`` unless given."""
-    _need(qkv, "qkv")
+    (q heads then k heads). Positions are ``token % seq`` unless given: then the
+    tables must hold ``seq`` rows; given, one int32 position per row of ``qkv``, on
+    its device, each below the tables' row count. Bad arguments raise before the
+    device is looked at, so nothing is launched with them."""
+    if qkv.dim() != 2:
+        raise ValueError("qkv must be a row-major 2-D matrix")
     for t in (cos, sin):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != head_dim // 2:
             raise ValueError("cos/sin must be contiguous fp32 [max_pos, head_dim/2]")
@@ -540,6 +544,14 @@ def rope_qkv_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: in
     if positions is not None:
         if positions.dtype != torch.int32 or not positions.is_contiguous():
             raise ValueError("positions must be contiguous int32")
+        if positions.dim() != 1 or positions.numel() != qkv.shape[0]:
+            raise ValueError("positions must be a 1-D tensor with one entry per row of qkv")
+        if positions.device != qkv.device:
+            raise ValueError("positions must be on qkv's device")
+    elif cos.shape[0] < seq or sin.shape[0] < seq:  # the kernel reads table row token % seq
+        raise ValueError("cos/sin must hold at least seq rows when no positions are given")
+    _need(qkv, "qkv")
+    if positions is not None:
         pos = positions.data_ptr()
     rc = _lib.lib().kgs_rope_qkv_bf16(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos, qkv.shape[0], heads,
                                       head_dim, qkv.stride(0), seq, _lib.stream_handle(qkv.device))

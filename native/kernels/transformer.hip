@@ -25,6 +25,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -69,6 +75,7 @@ __global__ __launch_bounds__(256) void add_rmsnorm(unsigned short* __restrict__ 
     for (int j = 0; j < NC; ++j) dv[j] = dr[lane + 64 * j];
   }
   float ss = 0.f;
+  double ssd = 0.0;  // Q8: the sum of squares once more in double, for the row scale alone
 #pragma unroll
   for (int j = 0; j < NC; ++j) {
     if (d != nullptr) {
@@ -82,6 +89,7 @@ __global__ __launch_bounds__(256) void add_rmsnorm(unsigned short* __restrict__ 
     for (int e = 0; e < 8; ++e) {
       v[j][e] = bf2f((unsigned short)xv[j][e]);
       ss += v[j][e] * v[j][e];
+      if constexpr (Q8) ssd += (double)v[j][e] * (double)v[j][e];
     }
   }
   if (d != nullptr) {
@@ -93,18 +101,25 @@ __global__ __launch_bounds__(256) void add_rmsnorm(unsigned short* __restrict__ 
   const float r = rsqrtf(ss / (float)(NC * 512) + eps);
   const bf16x8* wr = (const bf16x8*)w;
   if constexpr (Q8) {
-    float am = 0.f;
+    // The scale is held to an fp32 ulp of max|y| / 448: max|y| = max|x w| * rsqrt(..), the
+    // product of two bf16 is exact in fp32, and the root comes from the double sum -- y's
+    // own fp32 chain (sum, rsqrt, two products) is 2 ulp off before the division. The
+    // codes are quantised from the fp32 y as before; to_e4m3x8 clamps an ulp past 448.
+    float pm = 0.f;
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
       const bf16x8 wv = wr[lane + 64 * j];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        v[j][e] = v[j][e] * r * bf2f((unsigned short)wv[e]);
-        am = fmaxf(am, fabsf(v[j][e]));
+        const float wf = bf2f((unsigned short)wv[e]);
+        pm = fmaxf(pm, fabsf(v[j][e] * wf));
+        v[j][e] = v[j][e] * r * wf;
       }
     }
-    am = wave_max(am);
-    const float sc = fmaxf(am, 1e-12f) / E4M3_MAX, inv = 1.f / sc;
+    pm = wave_max(pm);
+    ssd = wave_sum(ssd);
+    const double rd = 1.0 / sqrt(ssd / (double)(NC * 512) + (double)eps);
+    const float sc = (float)(fmax((double)pm * rd, 1e-12) / (double)E4M3_MAX), inv = 1.f / sc;
     uint2* yq = (uint2*)((unsigned char*)y + row * ldy);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {

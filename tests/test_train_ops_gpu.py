@@ -13,12 +13,13 @@ import functools
 import pytest
 import torch
 
+# the criterion and the poisoned buffers are shared with the forward kernels' tests
+from forward_refs import POISON, poison_intact as _poison_intact, wide as _wide, within as _within
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-REL = 2.0 ** -7
 LP_TOL = 1e-4  # tests/test_logit_ops_gpu.py: an fp32 exp-sum's logprob, valid for |reference| <= 64
-POISON = 1234.0
 
 
 def _gen(seed):
@@ -29,30 +30,8 @@ def _randn(g, *shape, scale=1.0):
     return (scale * torch.randn(*shape, device=DEV, generator=g)).bfloat16()
 
 
-def _within(out, ref, atol, what):
-    """|out - ref| <= REL |ref| + atol elementwise (atol a number or a tensor); prints the margin."""
-    err = (out.double() - ref).abs()
-    slack = REL * ref.abs() + atol - err
-    print(f"{what}: max err {err.max().item():.3e}, least margin {slack.min().item():.3e}")
-    assert torch.isfinite(out.float()).all(), what
-    assert slack.min().item() >= 0, (what, err.max().item(), slack.min().item())
-
-
 def _zero_bits(t):
     return int(t.view(torch.int16).count_nonzero()) == 0
-
-
-def _wide(t, pad=64, off=8, extra_rows=2, fill=POISON):
-    """A copy of ``t`` as a view into a wider, taller poisoned buffer: (view, buffer)."""
-    buf = torch.full((t.shape[0] + extra_rows, t.shape[1] + pad), fill, dtype=t.dtype, device=t.device)
-    view = buf[:t.shape[0], off:off + t.shape[1]]
-    view.copy_(t)
-    return view, buf
-
-
-def _poison_intact(buf, rows, cols, off=8):
-    return bool((buf[:, :off] == POISON).all() and (buf[:, off + cols:] == POISON).all() and
-                (buf[rows:] == POISON).all())
 
 
 # ----------------------------------------------------------------------------
