@@ -1,6 +1,6 @@
 """A trainable pre-norm Llama decoder layer and a small language model over it:
-with ``backend="kgs"`` a whole training step, the embedding aside, runs on the
-HIP kernels.
+with ``backend="kgs"`` and ``embedding="kgs"`` a whole training step, from the
+token gather to the loss and back, runs on the HIP kernels.
 
 ``DecoderLayer``: ``rmsnorm -> QKV Linear -> RoPE -> flash attention -> o Linear``,
 then ``rmsnorm -> gate|up Linear -> SwiGLU -> down Linear``. The residual stream
@@ -23,8 +23,12 @@ fp32 reference copy, the PyTorch-ROCm comparison). Both backends start from the
 same seeded weights. ``linear="fp8"`` swaps the four projections (qkv, o, gate|up,
 down) for :class:`kgs.ops.LinearFp8` -- forward, dX and dW in e4m3 -- or, with
 ``backend="torch"``, for its torch model :class:`kgs.ops.RefLinearFp8`; the LM
-head and the embedding stay as they are. The reference has no model code;
-nothing here is ported.
+head and the embedding stay as they are. ``embedding="kgs"`` (with the kgs backend)
+swaps ``DecoderLM``'s ``nn.Embedding`` for :class:`kgs.ops.Embedding`: the gather
+and the deterministic dense scatter-sum of ``native/kernels/embedding.hip``; the
+default stays ``"torch"``. ``tie_embeddings=True`` makes the LM head's weight and
+the embedding's one Parameter, as the small Llama-3.2 models have it. The
+reference has no model code; nothing here is ported.
 """
 from __future__ import annotations
 
@@ -140,24 +144,42 @@ class DecoderLayer(torch.nn.Module):
 
 
 class DecoderLM(torch.nn.Module):
-    """Token embedding (torch), ``layers`` :class:`DecoderLayer`, a final norm and
-    an LM head; :meth:`loss` is the mean cross-entropy over the targets that are
-    not ignored (outside ``[0, vocab)``, e.g. -100)."""
+    """Token embedding, ``layers`` :class:`DecoderLayer`, a final norm and an LM
+    head; :meth:`loss` is the mean cross-entropy over the targets that are not
+    ignored (outside ``[0, vocab)``, e.g. -100).
+
+    ``embedding``: ``"torch"`` (``nn.Embedding``, the default) or ``"kgs"``
+    (:class:`kgs.ops.Embedding`; needs ``backend="kgs"`` and ``dim % 8 == 0``). The
+    parameter is ``embed.weight`` with the same seeded init either way.
+    ``tie_embeddings``: ``head.weight`` IS ``embed.weight``, one Parameter that
+    ``parameters()`` yields once (under ``embed.weight``); it takes the head's
+    init, ``randn * dim ** -0.5``, and its gradient is the sum of the two uses'."""
 
     def __init__(self, vocab: int, dim: int, layers: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs",
                  glue: str | None = None, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
-                 dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16"):
+                 dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", embedding: str = "torch",
+                 tie_embeddings: bool = False):
         super().__init__()
         if linear not in ("bf16", "fp8"):
             raise ValueError(f"linear must be 'bf16' or 'fp8', not {linear!r}")
+        if embedding not in ("torch", "kgs"):
+            raise ValueError(f"embedding must be 'torch' or 'kgs', not {embedding!r}")
+        if embedding == "kgs" and (backend != "kgs" or dim % 8):
+            raise ValueError("the kgs embedding takes the kgs backend and dim a multiple of 8")
         self.vocab, self.dim, self.eps, self.linear = vocab, dim, eps, linear
+        self.embedding, self.tie_embeddings = embedding, bool(tie_embeddings)
         self.layers = torch.nn.ModuleList(
             DecoderLayer(dim, heads, kv_heads, inter, backend=backend, glue=glue, rope_theta=rope_theta, eps=eps,
                          device=device, dtype=dtype, seed=seed + 1 + i, linear=linear) for i in range(layers))
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:
             raise ValueError("the kgs loss takes a vocabulary that is a multiple of 8")
-        self.embed = torch.nn.Embedding(vocab, dim, device=device, dtype=dtype)
+        if embedding == "kgs":
+            from kgs.ops.embedding import Embedding
+
+            self.embed = Embedding(vocab, dim, device=device)
+        else:
+            self.embed = torch.nn.Embedding(vocab, dim, device=device, dtype=dtype)
         self.norm = torch.nn.Parameter(torch.ones(dim, device=device, dtype=dtype))
         if backend == "kgs":
             from kgs.ops.gemm import Linear
@@ -169,6 +191,10 @@ class DecoderLM(torch.nn.Module):
         with torch.no_grad():  # identical init for both backends
             self.embed.weight.copy_(torch.randn(vocab, dim, generator=g))
             self.head.weight.copy_(torch.randn(vocab, dim, generator=g) * dim ** -0.5)
+            if tie_embeddings:  # the head's init, and the head's values of the untied model
+                self.embed.weight.copy_(self.head.weight)
+        if tie_embeddings:
+            self.head.weight = self.embed.weight
 
     def forward(self, tokens: torch.Tensor) -> torch.Tensor:
         """``tokens``: int64 ``[batch, seq]`` -> logits ``[batch * seq, vocab]``."""

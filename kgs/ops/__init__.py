@@ -19,6 +19,9 @@
   (``native/kernels/optimizer.hip``); the optimizer on them is :class:`kgs.optim.AdamW`
 * :func:`linear_fp8`, :class:`LinearFp8`, :func:`fp8_amax`, :func:`fp8_quantize`, :func:`ref_linear_fp8` --
   a trainable Linear whose forward, dX and dW GEMMs run in e4m3 (``native/kernels/fp8_train.hip``)
+* :func:`embedding`, :class:`Embedding`, :func:`embedding_rows`, :func:`embedding_rows_backward` --
+  a trainable token embedding: a row gather and a deterministic dense scatter-sum
+  (``native/kernels/embedding.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -55,4 +58,11 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         from . import fp8_train
 
         return getattr(fp8_train, name)
+    if name in ("embedding", "Embedding", "embedding_rows", "embedding_rows_backward", "ref_embedding_rows",
+                "ref_embedding_rows_backward"):
+        import importlib
+
+        # the op `embedding` shares its name with its module: the module is callable as the op
+        mod = importlib.import_module(".embedding", __name__)
+        return mod if name == "embedding" else getattr(mod, name)
     raise AttributeError(name)

@@ -89,6 +89,10 @@ _SIGS = {
     "kgs_silu_mul_bwd_bf16": ([_c_void_p] * 3 + [_c_long, _c_int] + [_c_long] * 3 + [_c_void_p], _c_int),
     "kgs_xent_fwd_bf16": ([_c_void_p] * 4 + [_c_int, _c_int, _c_long, _c_void_p], _c_int),
     "kgs_xent_bwd_bf16": ([_c_void_p] * 5 + [_c_int, _c_int, _c_long, _c_long, _c_void_p], _c_int),
+    # token embedding (native/kernels/embedding.hip)
+    "kgs_embed_fwd_bf16": ([_c_void_p] * 3 + [_c_int] * 3 + [_c_long, _c_long, ctypes.c_float, _c_void_p], _c_int),
+    "kgs_embed_bwd_bf16": ([_c_void_p] * 4 + [_c_int] * 3 + [_c_long, _c_long, ctypes.c_float, _c_long, _c_void_p],
+                           _c_int),
     # fp8 training producers (native/kernels/fp8_train.hip)
     "kgs_fp8_amax_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4, _c_int),
     "kgs_fp8_quant_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4 +
