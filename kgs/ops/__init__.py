@@ -17,6 +17,8 @@
 * :func:`adamw_table`, :func:`grad_norm`, :func:`adamw_step_` -- the fused AdamW step
   of every tensor of a model over a device-resident tensor table
   (``native/kernels/optimizer.hip``); the optimizer on them is :class:`kgs.optim.AdamW`
+* :func:`grad_accumulate_` -- the micro-batches' bf16 gradients summed into fp32 main
+  gradients that the step then reads (``native/kernels/grad_accum.hip``)
 * :func:`linear_fp8`, :class:`LinearFp8`, :func:`fp8_amax`, :func:`fp8_quantize`, :func:`ref_linear_fp8` --
   a trainable Linear whose forward, dX and dW GEMMs run in e4m3 (``native/kernels/fp8_train.hip``)
 * :func:`embedding`, :class:`Embedding`, :func:`embedding_rows`, :func:`embedding_rows_backward` --
@@ -50,7 +52,7 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
 
         return getattr(elementwise, name)
     if name in ("adamw_table", "adamw_step_", "grad_norm", "adamw_chunk", "ref_adamw_step", "ref_grad_norm",
-                "ref_clip"):
+                "ref_clip", "grad_accumulate_", "grad_accum_tables_check", "ref_grad_accumulate"):
         from . import optim
 
         return getattr(optim, name)

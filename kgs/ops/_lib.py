@@ -110,6 +110,13 @@ _SIGS = {
     "kgs_adamw_step": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p] + [ctypes.c_float] * 3 + [_c_void_p], _c_int),
     "kgs_adamw_step_v": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p] + [ctypes.c_float] * 3 +
                          [_c_int, _c_void_p], _c_int),
+    # fp32 main gradients (native/kernels/grad_accum.hip)
+    "kgs_grad_accum_table_check": ([_c_void_p, _c_void_p, _c_int], _c_int),
+    "kgs_grad_accumulate": ([_c_void_p, _c_void_p, _c_int, _c_long, _c_void_p, _c_int, _c_void_p], _c_int),
+    "kgs_main_sumsq": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p], _c_int),
+    "kgs_main_finalize": ([_c_void_p, _c_long] + [ctypes.c_float] * 3 + [_c_int, _c_void_p, _c_void_p], _c_int),
+    "kgs_adamw_step_main": ([_c_void_p, _c_int, _c_long, _c_void_p, _c_void_p] + [ctypes.c_float] * 3 +
+                            [_c_int, _c_void_p], _c_int),
     # paged prefill attention (native/kernels/attention_paged.hip)
     "kgs_attn_prefill_paged_bf16": ([_c_void_p] * 6 + [_c_int] * 6 + [_c_long] * 2 + [ctypes.c_float, _c_void_p],
                                     _c_int),

@@ -7,8 +7,12 @@ optimizer built on these.
 * :func:`grad_norm` -- the global gradient norm, the clip factor, the skip
   decision, the step counter and the bias corrections, into the device state block
 * :func:`adamw_step_` -- the update of every tensor of the table, in place
-* :func:`ref_adamw_step`, :func:`ref_grad_norm`, :func:`ref_clip` -- the same
-  formulas stated directly, float64 unless asked otherwise
+* :func:`grad_accumulate_` -- one micro-batch's bf16 gradients into fp32 main
+  gradients (``native/kernels/grad_accum.hip``); ``grad_norm`` and ``adamw_step_``
+  with ``main=True`` then step from those
+* :func:`ref_adamw_step`, :func:`ref_grad_norm`, :func:`ref_clip`,
+  :func:`ref_grad_accumulate` -- the same formulas stated directly, float64 unless
+  asked otherwise
 
 The step of all tensors is three launches (two without clipping) and no host
 synchronisation: lr, the step counter and the clip factor are read from device
@@ -25,6 +29,9 @@ ROW_WORDS = 8    # int64 words of a table row: w, p, m, v, g, numel, group, chun
 STATE_WORDS = 8  # 32-bit words of the state block
 # word index in the state block (ints: step, skipped, skip; the rest fp32)
 STATE_STEP, STATE_SKIPPED, STATE_GRAD_NORM, STATE_CLIP, STATE_BC1, STATE_BC2, STATE_SKIP = range(7)
+# word 7 (int), main gradients only: > 0 that many micro-batches are accumulated and wait for a step, <= 0 the
+# cycle is consumed (the last step left -n) and the next accumulate starts a fresh sum
+STATE_MICRO = 7
 
 
 def adamw_chunk() -> int:
@@ -54,15 +61,22 @@ def _on_gpu(named, dev=None):
     return dev
 
 
-def adamw_table(weights, masters, exp_avgs, exp_avg_sqs, grads, group_index, ngroups: int, pin: bool = True):
+def adamw_table(weights, masters, exp_avgs, exp_avg_sqs, grads, group_index, ngroups: int, pin: bool = True,
+                grad_dtype=torch.bfloat16):
     """The tensor table of :func:`grad_norm` / :func:`adamw_step_` as a host int64
     tensor ``[n, 8]`` (pinned unless ``pin`` is false), and its number of work chunks.
+    ``grad_dtype=torch.float32`` builds the main table of :func:`grad_accumulate_` and
+    of the ``main=True`` steps: ``grads`` are then the fp32 main gradients. Built from
+    the same tensors, the two tables have the same ``numel``, ``group`` and ``chunk0``
+    per row: row ``i`` and chunk ``c`` mean the same in both.
 
     Per tensor: a contiguous bf16 weight, contiguous fp32 master, first and second
     moment of the same number of elements, a contiguous bf16 gradient or ``None``
     (the tensor is skipped by the step) and the index of its parameter group. All on
     one GPU, every pointer 16-byte aligned; zero elements are legal. The checks
     here are the only ones: the kernels trust the table they are given."""
+    if grad_dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("grad_dtype must be torch.bfloat16 or torch.float32")
     n = len(weights)
     if not (len(masters) == len(exp_avgs) == len(exp_avg_sqs) == len(grads) == len(group_index) == n):
         raise ValueError("weights, masters, exp_avgs, exp_avg_sqs, grads and group_index need one entry per tensor")
@@ -75,7 +89,7 @@ def adamw_table(weights, masters, exp_avgs, exp_avg_sqs, grads, group_index, ngr
         _flat(exp_avgs[i], f"exp_avgs[{i}]", torch.float32, ne)
         _flat(exp_avg_sqs[i], f"exp_avg_sqs[{i}]", torch.float32, ne)
         if grads[i] is not None:
-            _flat(grads[i], f"grads[{i}]", torch.bfloat16, ne)
+            _flat(grads[i], f"grads[{i}]", grad_dtype, ne)
         if not 0 <= int(group_index[i]) < int(ngroups):
             raise ValueError(f"group_index[{i}] must be in [0, {int(ngroups)})")
     dev = None
@@ -136,8 +150,50 @@ def _betas(betas):
     return b1, b2
 
 
+def grad_accum_tables_check(grad_host: torch.Tensor, main_host: torch.Tensor) -> None:
+    """The host-side check of the pair of tables :func:`grad_accumulate_` takes (both
+    from :func:`adamw_table`, before they are uploaded): row for row the same
+    ``numel``, ``group`` and ``chunk0``, and a main gradient for every tensor that has
+    elements. The kernel trusts the device copies."""
+    for t, name in ((grad_host, "grad_host"), (main_host, "main_host")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+            raise TypeError(f"{name} must be an int64 tensor (adamw_table's)")
+        if t.is_cuda or t.dim() != 2 or t.shape[1] != ROW_WORDS or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous host [n, {ROW_WORDS}] tensor")
+    if grad_host.shape != main_host.shape:
+        raise ValueError("the two tables need the same number of rows")
+    rc = int(_lib.lib().kgs_grad_accum_table_check(grad_host.data_ptr(), main_host.data_ptr(), grad_host.shape[0]))
+    _lib.check(rc, "grad_accum_tables_check")
+
+
+def grad_accumulate_(grad_table: torch.Tensor, main_table: torch.Tensor, nchunks: int, state: torch.Tensor,
+                     zero_grads: bool = True) -> None:
+    """One micro-batch into the fp32 main gradients of every tensor, in one launch
+    over the two device tables, and a one-thread launch behind it that advances the
+    micro-batch count (word 7 of ``state``). Per element ``main = float(g)`` when the
+    count says that the cycle is consumed (<= 0: the first micro-batch), ``main = main +
+    float(g)`` otherwise: one fp32 add. With ``zero_grads`` the bf16 gradient is left
+    as zero bits in the same pass. A row without a bf16 gradient contributes nothing;
+    on a first micro-batch its main gradient is written as zeros."""
+    for t in (grad_table, main_table):  # both types before any device check
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+            raise TypeError("grad_table and main_table must be int64 tensors (adamw_table's, copied to the GPU)")
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int32:
+        raise TypeError("state must be an int32 tensor")
+    if grad_table.shape != main_table.shape:
+        raise ValueError("the two tables need the same number of rows")
+    _device_blocks(grad_table, nchunks, state)
+    _device_blocks(main_table, nchunks, state)
+    _on_gpu(((grad_table, "grad_table"), (main_table, "main_table")))
+    rc = _lib.lib().kgs_grad_accumulate(grad_table.data_ptr(), main_table.data_ptr(), grad_table.shape[0],
+                                        int(nchunks), state.data_ptr(), 1 if zero_grads else 0,
+                                        _lib.stream_handle(grad_table.device))
+    _lib.check(rc, "grad_accumulate_")
+
+
 def grad_norm(table: torch.Tensor, nchunks: int, state: torch.Tensor, betas, partials: torch.Tensor | None = None,
-              max_norm: float | None = None, variant: int | None = None) -> None:
+              max_norm: float | None = None, variant: int | None = None, main: bool = False,
+              average: bool = True) -> None:
     """The scalar half of a step, into the device ``state`` block (int32 ``[8]``).
 
     With ``max_norm``: one fp32 sum of squares of the bf16 gradients per chunk into
@@ -149,14 +205,31 @@ def grad_norm(table: torch.Tensor, nchunks: int, state: torch.Tensor, betas, par
     not skipped increments ``step`` and gets ``bc1 = 1 - b1^step``, ``bc2 = 1 -
     b2^step``, evaluated in double. Two launches (one without clipping), no atomics:
     bitwise repeatable. ``variant``: odd reads the gradients with non-temporal loads
-    (the measured default), even with plain ones."""
+    (the measured default), even with plain ones.
+
+    ``main=True``: ``table`` is the fp32 main table. The norm is that of ``s * main``
+    with ``s = 1 / n`` for ``average`` (``n`` the micro-batch count of the state block)
+    and 1 otherwise; the cycle is consumed whether the step is skipped or not, and a
+    step with nothing accumulated counts as skipped. There are no variants."""
     _device_blocks(table, nchunks, state, partials=partials)
     b1, b2 = _betas(betas)
     if (max_norm is None) != (partials is None):
         raise ValueError("max_norm and partials come together")
     if max_norm is not None and not float(max_norm) > 0.0:
         raise ValueError("max_norm must be positive")
+    if main and variant is not None:
+        raise ValueError("the main-gradient norm pass has no variants")
     lib, st = _lib.lib(), _lib.stream_handle(table.device)
+    if main:
+        avg = 1 if average else 0
+        if max_norm is None or int(nchunks) == 0:
+            _lib.check(lib.kgs_main_finalize(0, 0, 1.0, b1, b2, avg, state.data_ptr(), st), "grad_norm")
+            return
+        _lib.check(lib.kgs_main_sumsq(table.data_ptr(), table.shape[0], int(nchunks), partials.data_ptr(), st),
+                   "grad_norm")
+        _lib.check(lib.kgs_main_finalize(partials.data_ptr(), int(nchunks), float(max_norm), b1, b2, avg,
+                                         state.data_ptr(), st), "grad_norm")
+        return
     if max_norm is None or int(nchunks) == 0:
         _lib.check(lib.kgs_adamw_finalize(0, 0, 1.0, b1, b2, state.data_ptr(), st), "grad_norm")
         return
@@ -168,7 +241,7 @@ def grad_norm(table: torch.Tensor, nchunks: int, state: torch.Tensor, betas, par
 
 
 def adamw_step_(table: torch.Tensor, nchunks: int, groups: torch.Tensor, state: torch.Tensor, betas, eps: float,
-                variant: int | None = None) -> None:
+                variant: int | None = None, main: bool = False, average: bool = True) -> None:
     """AdamW on every tensor of the table that has a gradient, in place, one launch.
     Per element, in fp32, with ``clip``, ``bc1``, ``bc2`` and the skip flag from
     ``state`` (:func:`grad_norm` ran before) and ``lr``, ``wd`` from the tensor's row
@@ -182,12 +255,24 @@ def adamw_step_(table: torch.Tensor, nchunks: int, groups: torch.Tensor, state: 
     rounded to nearest even, once. On a skipped step nothing is written.
     ``variant``: 0 plain accesses, 1 non-temporal, 2 / 3 the same with two 16-byte
     groups per thread and trip, 4 / 5 two groups with non-temporal loads / stores
-    only; ``None`` is the measured default (2)."""
+    only; ``None`` is the measured default (2).
+
+    ``main=True``: ``table`` is the fp32 main table and ``g = clip * s * main`` with
+    the ``s`` of :func:`grad_norm` (which ran before with the same ``average``); the
+    same arithmetic otherwise, two groups per trip and plain accesses, no variants."""
     _device_blocks(table, nchunks, state, groups=groups)
     b1, b2 = _betas(betas)
     if not float(eps) >= 0.0:
         raise ValueError("eps must not be negative")
     lib = _lib.lib()
+    if main:
+        if variant is not None:
+            raise ValueError("the main-gradient step has no variants")
+        rc = lib.kgs_adamw_step_main(table.data_ptr(), table.shape[0], int(nchunks), groups.data_ptr(),
+                                     state.data_ptr(), b1, b2, float(eps), 1 if average else 0,
+                                     _lib.stream_handle(table.device))
+        _lib.check(rc, "adamw_step_")
+        return
     v = int(lib.kgs_adamw_step_default_variant()) if variant is None else int(variant)
     rc = lib.kgs_adamw_step_v(table.data_ptr(), table.shape[0], int(nchunks), groups.data_ptr(), state.data_ptr(),
                               b1, b2, float(eps), v, _lib.stream_handle(table.device))
@@ -197,25 +282,35 @@ def adamw_step_(table: torch.Tensor, nchunks: int, groups: torch.Tensor, state: 
 # ----------------------------------------------------------------------------
 # references: the formulas, stated directly
 
-def ref_adamw_step(p, m, v, g, step, lr, betas, eps, weight_decay, clip=1.0, dtype=torch.float64):
+def ref_adamw_step(p, m, v, g, step, lr, betas, eps, weight_decay, clip=1.0, dtype=torch.float64, scale=1.0):
     """``(p, m, v)`` after AdamW step number ``step`` (1 for the first) in ``dtype``,
-    unrounded: decoupled weight decay, bias-corrected moments, ``g`` scaled by ``clip``."""
+    unrounded: decoupled weight decay, bias-corrected moments, ``g`` scaled by ``clip``
+    and by ``scale`` (a main-gradient step's ``1 / n``)."""
     b1, b2 = betas
-    pf, mf, vf, gf = p.to(dtype), m.to(dtype), v.to(dtype), clip * g.to(dtype)
+    pf, mf, vf, gf = p.to(dtype), m.to(dtype), v.to(dtype), (clip * scale) * g.to(dtype)
     mf = b1 * mf + (1 - b1) * gf
     vf = b2 * vf + (1 - b2) * gf * gf
     bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
     return pf * (1 - lr * weight_decay) - lr * (mf / bc1) / ((vf / bc2).sqrt() + eps), mf, vf
 
 
-def ref_grad_norm(grads, dtype=torch.float64):
-    """The 2-norm of all gradients taken as one vector, in ``dtype``; ``None`` entries
-    do not count."""
+def ref_grad_norm(grads, dtype=torch.float64, scale=1.0):
+    """The 2-norm of all gradients, each times ``scale``, taken as one vector, in
+    ``dtype``; ``None`` entries do not count."""
     total = torch.zeros((), dtype=dtype)
     for g in grads:
         if g is not None:
-            total = total + g.to(dtype).pow(2).sum().to(total.device)
+            total = total + (scale * g.to(dtype)).pow(2).sum().to(total.device)
     return total.sqrt()
+
+
+def ref_grad_accumulate(main, grad, first: bool, dtype=torch.float64):
+    """The main gradient after one micro-batch, in ``dtype``, unrounded: ``grad`` on
+    the first micro-batch of a cycle (zeros for a ``None`` gradient), ``main + grad``
+    afterwards (``main`` for a ``None`` gradient)."""
+    if first:
+        return torch.zeros_like(main, dtype=dtype) if grad is None else grad.to(dtype)
+    return main.to(dtype) if grad is None else main.to(dtype) + grad.to(dtype)
 
 
 def ref_clip(norm, max_norm):

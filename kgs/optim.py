@@ -13,6 +13,13 @@ tensor table; ``backend="torch"`` is the same algorithm in plain torch fp32 ops,
 on any device. Both keep lr, the step counter, the clip factor and the skip
 decision on the device: nothing in ``step()`` waits for the GPU, and with
 ``zero_grad(set_to_none=False)`` a step can be captured in ``torch.cuda.graph``.
+
+``main_grads=True`` adds fp32 main gradients for training with micro-batches:
+``accumulate()`` after each ``backward()`` folds the bf16 ``.grad`` of every tensor
+into them in one launch of ``native/kernels/grad_accum.hip`` (and zeroes ``.grad``
+in the same pass), and ``step()`` reads them instead of ``.grad``. A bf16 running
+sum, which is what ``p.grad += ...`` keeps, rounds once per micro-batch relative
+to the sum; the fp32 sum keeps what the fp32 masters were built to keep.
 """
 from __future__ import annotations
 
@@ -62,17 +69,33 @@ class AdamW(torch.optim.Optimizer):
     and the parameters' and gradients' addresses, and uploads the group block or the
     tensor table only when they changed. A captured step replays the addresses it
     was captured with; after changing a group's ``lr`` between replays call
-    :meth:`update_groups`."""
+    :meth:`update_groups`.
+
+    ``main_grads=True``: a fourth flat fp32 buffer, ``main_grad``, laid out like the
+    masters (:meth:`main_grad` is a tensor's view of it). :meth:`accumulate` after
+    each micro-batch's ``backward()`` sets it to ``float(grad)`` on the first
+    micro-batch of a cycle and adds ``float(grad)`` afterwards, one fp32 add per
+    element; ``step()`` then ignores ``.grad`` and takes ``s * main_grad`` as the
+    gradient, ``s = 1 / n`` over the ``n`` micro-batches of the cycle with
+    ``grad_average`` and 1 without. ``grad_norm`` is the norm of that scaled
+    gradient. Applied or skipped, a step consumes the cycle: the next
+    ``accumulate()`` starts a fresh sum. A parameter that had no gradient at any
+    ``accumulate()`` of the cycle is left alone. The micro-batch count lives in the
+    device state block, so one captured ``accumulate()`` and one captured ``step()``
+    replay cycles of any length; a replayed step with nothing accumulated counts
+    as skipped, an eager one raises. Main gradients are not part of
+    ``state_dict()``."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_grad_norm: float | None = None, backend: str = "kgs", amsgrad: bool = False,
-                 maximize: bool = False):
+                 maximize: bool = False, main_grads: bool = False, grad_average: bool = True):
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', got {backend!r}")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be positive")
         self.backend = backend
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.main_grads, self.grad_average = bool(main_grads), bool(grad_average)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
                                       maximize=maximize))
         self._check_groups()
@@ -100,12 +123,21 @@ class AdamW(torch.optim.Optimizer):
             seg = {k: f[off:off + p.numel()].view(p.shape) for k, f in self._flat.items()}
             seg["master"].copy_(p.detach())  # bf16 -> fp32 is exact
             self.state[p] = {"step": torch.zeros((), dtype=torch.float32), **seg}
+        self._main = {}
+        if self.main_grads:  # not optimizer state: never checkpointed
+            self._flat["main_grad"] = torch.zeros_like(self._flat["master"])
+            self._main = {p: self._flat["main_grad"][off:off + p.numel()].view(p.shape)
+                          for p, off in zip(self._params, self._offsets)}
         # device blocks: the step's scalars (kgs.ops.optim.STATE_*) and {lr, weight_decay} per group
         self._state = torch.zeros(_ops.STATE_WORDS, dtype=torch.int32, device=dev)
         self._state.view(torch.float32)[_ops.STATE_CLIP] = 1.0
         self._groups = torch.zeros((len(self.param_groups), 2), dtype=torch.float32, device=dev)
         self._group_key = None
         self._table = self._partials = self._table_key = None
+        # main gradients: the table of all of them (accumulate) and of those the cycle gave a gradient (step)
+        self._main_all = self._main_all_key = self._main_live = self._main_live_key = None
+        self._host_tables = {}
+        self._host_micro, self._cycle_live = 0, set()  # accumulate() calls since the last step, who had a gradient
         self._nchunks = 0
         self.table_refreshes = 0
         self.group_refreshes = 0
@@ -158,25 +190,85 @@ class AdamW(torch.optim.Optimizer):
         self.group_refreshes += 1
         return True
 
-    def _update_table(self) -> None:
-        key = tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr()) for p in self._params)
-        if key == self._table_key:
-            return
+    def _update_table(self, which: str = "_table", live=None) -> bool:
+        """Upload table ``which`` if an address in it changed; returns whether it did.
+        ``_table``: the bf16 ``.grad`` as gradients. ``_main_all`` / ``_main_live``: the
+        fp32 main gradients of every tensor / of the tensors in ``live``."""
+        if which == "_table":
+            grads = [None if p.grad is None else p.grad.reshape(-1) for p in self._params]
+        else:
+            grads = [self._main[p].reshape(-1) if live is None or i in live else None
+                     for i, p in enumerate(self._params)]
+        key = tuple((p.data_ptr(), 0 if g is None else g.data_ptr()) for p, g in zip(self._params, grads))
+        if key == getattr(self, which + "_key"):
+            return False
         st = [self.state[p] for p in self._params]
         host, nchunks = _ops.adamw_table([p.detach().reshape(-1) for p in self._params],
                                          [s["master"].reshape(-1) for s in st],
                                          [s["exp_avg"].reshape(-1) for s in st],
                                          [s["exp_avg_sq"].reshape(-1) for s in st],
-                                         [None if p.grad is None else p.grad.reshape(-1) for p in self._params],
-                                         self._group_of, len(self.param_groups))
-        if self._table is None:
-            self._table = torch.empty_like(host, device=self.device)
+                                         grads, self._group_of, len(self.param_groups),
+                                         grad_dtype=torch.bfloat16 if which == "_table" else torch.float32)
+        if getattr(self, which) is None:
+            setattr(self, which, torch.empty_like(host, device=self.device))
+        if self._partials is None:
             self._partials = torch.empty(max(nchunks, 4), dtype=torch.float32, device=self.device)
-        assert nchunks == self._nchunks or self._table_key is None  # numels do not change
+        assert self._nchunks in (0, nchunks)  # numels do not change
         self._nchunks = nchunks
-        self._upload(self._table, host)
-        self._table_key = key
+        self._upload(getattr(self, which), host)
+        self._host_tables[which] = host
+        setattr(self, which + "_key", key)
         self.table_refreshes += 1
+        return True
+
+    # ------------------------------------------------------------------ main gradients
+
+    def main_grad(self, p: torch.Tensor) -> torch.Tensor:
+        """The fp32 main gradient of parameter ``p``: a view of the flat buffer."""
+        if not self.main_grads:
+            raise RuntimeError("main_grad() needs AdamW(main_grads=True)")
+        return self._main[p]
+
+    @torch.no_grad()
+    def accumulate(self, zero_grads: bool = True) -> None:
+        """Fold every parameter's ``.grad`` into its fp32 main gradient; call it after
+        each micro-batch's ``backward()``. The first call of a cycle overwrites
+        (``main = float(grad)``), the later ones add (one fp32 add per element). With
+        ``zero_grads`` the gradients are zeroed in the same pass and stay allocated
+        where they are, so the next ``backward()`` accumulates into zeros and no
+        ``zero_grad()`` is needed. A ``.grad`` that is ``None`` contributes nothing; on
+        the first call of a cycle that tensor's main gradient is written as zeros. The
+        kgs backend: one launch over the tensor table and a one-thread launch that
+        advances the device's micro-batch count, no host synchronisation."""
+        if not self.main_grads:
+            raise RuntimeError("accumulate() needs AdamW(main_grads=True)")
+        live = {i for i, p in enumerate(self._params) if p.grad is not None}
+        if self.backend == "kgs":
+            self._check_grads()
+            a, b = self._update_table(), self._update_table("_main_all")
+            if a or b:
+                _ops.grad_accum_tables_check(self._host_tables["_table"], self._host_tables["_main_all"])
+            _ops.grad_accumulate_(self._table, self._main_all, self._nchunks, self._state, zero_grads=zero_grads)
+        else:
+            micro = self._state[_ops.STATE_MICRO]
+            first = micro <= 0
+            for p in self._params:
+                a = self._main[p]
+                if p.grad is None:
+                    a.copy_(torch.where(first, torch.zeros_like(a), a))
+                    continue
+                g = p.grad.float()
+                a.copy_(torch.where(first, g, a + g))
+                if zero_grads:
+                    p.grad.zero_()
+            self._state[_ops.STATE_MICRO] = torch.where(first, torch.ones_like(micro), micro + 1)
+        self._cycle_live |= live
+        self._host_micro += 1
+
+    def _check_grads(self) -> None:
+        for p in self._params:
+            if p.grad is not None and (p.grad.dtype != torch.bfloat16 or not p.grad.is_contiguous()):
+                raise ValueError("the kgs backend needs contiguous bf16 gradients")
 
     # ------------------------------------------------------------------ the step
 
@@ -186,10 +278,10 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if self.backend == "kgs":
-            for p in self._params:
-                if p.grad is not None and (p.grad.dtype != torch.bfloat16 or not p.grad.is_contiguous()):
-                    raise ValueError("the kgs backend needs contiguous bf16 gradients")
+        if self.main_grads:
+            self._step_main()
+        elif self.backend == "kgs":
+            self._check_grads()
             self._update_table()
             self.update_groups()
             clipping = self.max_grad_norm is not None
@@ -201,19 +293,47 @@ class AdamW(torch.optim.Optimizer):
             self._step_torch()
         return loss
 
-    def _step_torch(self) -> None:
-        """The kernels' algorithm in torch fp32 ops; the skip is a select, not a branch."""
-        live = [(i, p) for i, p in enumerate(self._params) if p.grad is not None]
+    def _step_main(self) -> None:
+        """A step from the main gradients of the tensors the cycle gave a gradient."""
+        if self._host_micro == 0:
+            raise RuntimeError("step() with nothing accumulated: call accumulate() after each backward()")
+        live = self._cycle_live
+        self.update_groups()
+        if self.backend == "kgs":
+            self._update_table("_main_live", live)
+            clipping = self.max_grad_norm is not None
+            _ops.grad_norm(self._main_live, self._nchunks, self._state, self.betas,
+                           partials=self._partials if clipping else None, max_norm=self.max_grad_norm, main=True,
+                           average=self.grad_average)
+            _ops.adamw_step_(self._main_live, self._nchunks, self._groups, self._state, self.betas, self.eps,
+                             main=True, average=self.grad_average)
+        else:
+            micro = self._state[_ops.STATE_MICRO]
+            has = micro > 0
+            s = 1.0 / micro.clamp(min=1).float() if self.grad_average else torch.ones((), device=self.device)
+            self._step_torch([(i, p, s * self._main[p]) for i, p in enumerate(self._params) if i in live], has)
+            self._state[_ops.STATE_MICRO] = torch.where(has, -micro, micro)
+        self._host_micro, self._cycle_live = 0, set()
+
+    def _step_torch(self, live=None, has=None) -> None:
+        """The kernels' algorithm in torch fp32 ops; the skip is a select, not a branch.
+        ``live``: ``(index, parameter, gradient)`` of the tensors to step, by default
+        those with a ``.grad``; ``has``: a device flag that must hold for the step to
+        be applied (main gradients: something was accumulated)."""
+        if live is None:
+            live = [(i, p, p.grad) for i, p in enumerate(self._params) if p.grad is not None]
         sf, si = self._state.view(torch.float32), self._state
         b1, b2 = self.betas
         if self.max_grad_norm is not None and live:
-            norm = _sumsq([p.grad for _, p in live]).sqrt()
+            norm = _sumsq([g for _, _, g in live]).sqrt()
             ok = torch.isfinite(norm)
             clip = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
             sf[_ops.STATE_GRAD_NORM] = norm
         else:
             ok = torch.ones((), dtype=torch.bool, device=self.device)
             clip = torch.ones((), dtype=torch.float32, device=self.device)
+        if has is not None:
+            ok = ok & has
         si[_ops.STATE_SKIP] = (~ok).to(torch.int32)
         si[_ops.STATE_SKIPPED] += (~ok).to(torch.int32)
         si[_ops.STATE_STEP] += ok.to(torch.int32)
@@ -223,10 +343,10 @@ class AdamW(torch.optim.Optimizer):
         bc1, bc2 = torch.where(ok, bc1, sf[_ops.STATE_BC1]), torch.where(ok, bc2, sf[_ops.STATE_BC2])
         sf[_ops.STATE_CLIP] = torch.where(ok, clip, sf[_ops.STATE_CLIP])
         sf[_ops.STATE_BC1], sf[_ops.STATE_BC2] = bc1, bc2
-        for i, p in live:
+        for i, p, grad in live:
             s = self.state[p]
             lr, wd = self._groups[self._group_of[i]]
-            g = clip * p.grad.float()
+            g = clip * grad.float()
             m = b1 * s["exp_avg"] + (1 - b1) * g
             v = b2 * s["exp_avg_sq"] + (1 - b2) * g * g
             new = s["master"] * (1 - lr * wd) - lr * (m / bc1) / ((v / bc2).sqrt() + self.eps)
@@ -259,6 +379,11 @@ class AdamW(torch.optim.Optimizer):
     def skipped_steps(self) -> int:
         return self._word(_ops.STATE_SKIPPED, False)
 
+    @property
+    def pending_micro_batches(self) -> int:
+        """Micro-batches accumulated since the last step, as the device counts them."""
+        return max(self._word(_ops.STATE_MICRO, False), 0)
+
     # ------------------------------------------------------------------ checkpoints
 
     def state_dict(self):
@@ -270,7 +395,9 @@ class AdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def load_state_dict(self, state_dict) -> None:
         """torch's layout; ``torch.optim.Optimizer.load_state_dict`` itself would cast
-        the fp32 state to the parameters' bf16, so the tensors are copied here."""
+        the fp32 state to the parameters' bf16, so the tensors are copied here. Main
+        gradients are not checkpointed: loading resets the accumulation cycle, and
+        whatever was accumulated and not yet stepped is dropped."""
         saved = state_dict["param_groups"]
         if len(saved) != len(self.param_groups) or any(len(s["params"]) != len(g["params"])
                                                        for s, g in zip(saved, self.param_groups)):
@@ -300,3 +427,4 @@ class AdamW(torch.optim.Optimizer):
         block.view(torch.float32)[_ops.STATE_CLIP] = 1.0
         self._upload(self._state, block)
         self._group_key = None
+        self._host_micro, self._cycle_live = 0, set()

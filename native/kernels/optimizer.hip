@@ -26,7 +26,8 @@
 //   group block: float {lr, weight_decay} per group.
 //   state block, eight 32-bit words:
 //     0 step (int)  1 skipped (int)  2 grad_norm  3 clip  4 bc1 = 1 - b1^step
-//     5 bc2 = 1 - b2^step  6 skip flag of the current step (int)  7 unused
+//     5 bc2 = 1 - b2^step  6 skip flag of the current step (int)
+//     7 micro-batch count of grad_accum.hip (int), untouched by this file
 //
 // lr, the step counter and the clip factor live on the device so that a captured
 // step replays with new values: nothing of them is baked into a kernel argument.
@@ -37,9 +38,7 @@
 //
 // House rules (train_ops.hip): 16-B accesses, no allocation or synchronisation
 // in an entry, nothing launched for empty work.
-#include "kgs_common.h"
-
-#define KGS_ADAMW_CHUNK 16384
+#include "optimizer_common.h"
 
 namespace kgs {
 namespace opt {
@@ -47,62 +46,6 @@ namespace opt {
 // the __global__ functions of this file, template instantiations counted once
 // each (tests/test_optim.py compares it with what the compiler reports)
 constexpr int KERNEL_COUNT = 9;
-
-constexpr int CHUNK = KGS_ADAMW_CHUNK;
-constexpr int THREADS = 256;
-constexpr int SPAN = THREADS * 8;  // elements one trip of the workgroup covers
-
-struct Row {
-  unsigned short* w;
-  float* p;
-  float* m;
-  float* v;
-  const unsigned short* g;
-  long numel;
-  long group;
-  long chunk0;
-};
-static_assert(sizeof(Row) == 64, "table row layout");
-
-struct State {
-  int step;
-  int skipped;
-  float grad_norm;
-  float clip;
-  float bc1;
-  float bc2;
-  int skip;
-  int pad;
-};
-static_assert(sizeof(State) == 32, "state block layout");
-
-// the last row whose chunk0 <= chunk: rows without chunks (numel 0) share their
-// chunk0 with the next row and are passed over
-__device__ __forceinline__ int find_row(const Row* __restrict__ rows, int n, long chunk) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rows[mid].chunk0 <= chunk) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The tensors' pointers come out of the table, so hipcc cannot know their address
-// space and would emit flat_ loads and stores; they are global memory.
-template <bool NT, class T>
-__device__ __forceinline__ T ld(const T* p) {
-  const KGS_GLB T* q = (const KGS_GLB T*)p;
-  if constexpr (NT) return __builtin_nontemporal_load(q);
-  else return *q;
-}
-
-template <bool NT, class T>
-__device__ __forceinline__ void st(T* p, T v) {
-  KGS_GLB T* q = (KGS_GLB T*)p;
-  if constexpr (NT) __builtin_nontemporal_store(v, q);
-  else *q = v;
-}
 
 // ---------------------------------------------------------------------------
 // One partial per chunk. A thread owns the 16-B groups tid, tid + 256, ... of
@@ -189,32 +132,8 @@ __global__ __launch_bounds__(1024) void finalize(const float* __restrict__ parti
 }
 
 // ---------------------------------------------------------------------------
-// The update of one element. The constants are wave-uniform and made once per
-// thread in double: k1 = (1 - b1) clip and k2 = (1 - b2) clip^2 as unevaluated
-// fp32 pairs (hi + lo), decay = 1 - lr wd rounded once.
-//
-// m' = b1 m + k1 g cancels when the gradient turns against the momentum, and a
-// rounded product k1 g would then leave an error that is relative to the
-// product, not to m'. So the product's own rounding error (one fma) and the
-// low half of k1 are added back after the sum: m' and v' carry two roundings of
-// the RESULT, |err| <= 2^-23 |m'|, for any clip. g^2 is exact in fp32 (bf16 has
-// 8 significant bits).
-struct Consts {
-  float b1, b2, k1h, k1l, k2h, k2l, decay, lr, bc1, bc2, eps;
-};
-
-__device__ __forceinline__ void update(const Consts& c, float g, float& p, float& m, float& v) {
-  const float t1 = c.k1h * g;
-  const float e1 = __builtin_fmaf(c.k1l, g, __builtin_fmaf(c.k1h, g, -t1));
-  m = __builtin_fmaf(c.b1, m, t1) + e1;
-  const float g2 = g * g;
-  const float t2 = c.k2h * g2;
-  const float e2 = __builtin_fmaf(c.k2l, g2, __builtin_fmaf(c.k2h, g2, -t2));
-  v = __builtin_fmaf(c.b2, v, t2) + e2;
-  const float u = (m / c.bc1) / (__builtin_sqrtf(v / c.bc2) + c.eps);
-  p = __builtin_fmaf(p, c.decay, -(c.lr * u));
-}
-
+// The update of one element, its constants and their error analysis:
+// optimizer_common.h (Consts, update).
 struct Regs {
   bf16x8 g;
   f32x4 p[2], m[2], v[2];
