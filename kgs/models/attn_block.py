@@ -31,9 +31,22 @@ def _rope(qkv: torch.Tensor, batch: int, seq: int, rot_heads: int, head_dim: int
     return torch.cat((rot.to(qkv.dtype), qkv[:, rot_heads * head_dim:]), dim=1)
 
 
+def _qknorm_rope(qkv: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, seq: int, heads: int, kv_heads: int,
+                 theta: float, eps: float) -> torch.Tensor:
+    """QK-norm and rotate-half RoPE in torch ops: :func:`kgs.ops.ref_qknorm_rope` in
+    fp32 (float64 for a float64 model), rounded once to ``qkv``'s dtype."""
+    from kgs.ops.qknorm_rope import ref_qknorm_rope
+    from kgs.ops.transformer import rope_tables
+
+    cos, sin = rope_tables(seq, 128, theta, qkv.device)
+    up = torch.promote_types(qkv.dtype, torch.float32)
+    return ref_qknorm_rope(qkv, wq, wk, cos, sin, heads, kv_heads, seq, eps=eps, dtype=up).to(qkv.dtype)
+
+
 class AttentionBlock(torch.nn.Module):
     def __init__(self, dim: int, heads: int, kv_heads: int, backend: str = "kgs", causal: bool = True,
-                 rope_theta: float = 10000.0, device=None, dtype=torch.bfloat16, seed: int = 0):
+                 rope_theta: float = 10000.0, device=None, dtype=torch.bfloat16, seed: int = 0,
+                 qk_norm: bool = False, qk_norm_eps: float = 1e-6):
         super().__init__()
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', not {backend!r}")
@@ -41,6 +54,9 @@ class AttentionBlock(torch.nn.Module):
             raise ValueError("dim must divide by heads and heads by kv_heads")
         self.backend, self.dim, self.heads, self.kv_heads = backend, dim, heads, kv_heads
         self.head_dim, self.causal, self.rope_theta = dim // heads, causal, rope_theta
+        self.qk_norm, self.qk_norm_eps = bool(qk_norm), qk_norm_eps
+        if self.qk_norm and self.head_dim != 128:
+            raise ValueError("qk_norm takes head_dim 128")
         if backend == "kgs" and (self.head_dim != 128 or dtype != torch.bfloat16):
             raise ValueError("the kgs backend takes head_dim 128 and bf16")
         wqkv = (heads + 2 * kv_heads) * self.head_dim
@@ -56,13 +72,19 @@ class AttentionBlock(torch.nn.Module):
         with torch.no_grad():  # identical init for both backends
             self.qkv.weight.copy_(torch.randn(wqkv, dim, generator=g) * dim ** -0.5)
             self.o.weight.copy_(torch.randn(dim, dim, generator=g) * dim ** -0.5)
+        if self.qk_norm:
+            self.q_norm = torch.nn.Parameter(torch.ones(self.head_dim, device=device, dtype=dtype))
+            self.k_norm = torch.nn.Parameter(torch.ones(self.head_dim, device=device, dtype=dtype))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """``x``: ``[batch, seq, dim]`` -> ``[batch, seq, dim]``."""
         b, s, _ = x.shape
         nh, nkv, hd = self.heads, self.kv_heads, self.head_dim
         qkv = self.qkv(x.reshape(b * s, self.dim))
-        qkv = _rope(qkv, b, s, nh + nkv, hd, self.rope_theta)
+        if self.qk_norm:  # like this block's RoPE: torch ops (DecoderLayer's kgs glue has the kernel)
+            qkv = _qknorm_rope(qkv, self.q_norm, self.k_norm, s, nh, nkv, self.rope_theta, self.qk_norm_eps)
+        else:
+            qkv = _rope(qkv, b, s, nh + nkv, hd, self.rope_theta)
         if self.backend == "kgs":
             from kgs.ops.transformer import flash_attention_qkv
 

@@ -27,14 +27,18 @@ head and the embedding stay as they are. ``embedding="kgs"`` (with the kgs backe
 swaps ``DecoderLM``'s ``nn.Embedding`` for :class:`kgs.ops.Embedding`: the gather
 and the deterministic dense scatter-sum of ``native/kernels/embedding.hip``; the
 default stays ``"torch"``. ``tie_embeddings=True`` makes the LM head's weight and
-the embedding's one Parameter, as the small Llama-3.2 models have it. The
-reference has no model code; nothing here is ported.
+the embedding's one Parameter, as the small Llama-3.2 models have it.
+``qk_norm=True`` (Qwen3, OLMo-2, Gemma-3) gives every layer ``q_norm`` and ``k_norm``
+Parameters ``[128]`` and normalises each head of q and of k before the rotation:
+with the kgs glue on :func:`kgs.ops.qknorm_rope` in place of :func:`kgs.ops.rope_qkv`,
+otherwise in torch ops in fp32; off, the layer is exactly the one without the
+option. The reference has no model code; nothing here is ported.
 """
 from __future__ import annotations
 
 import torch
 
-from .attn_block import _rope
+from .attn_block import _qknorm_rope, _rope
 
 
 def _torch_rmsnorm(res: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
@@ -52,7 +56,8 @@ def _torch_swiglu(gu: torch.Tensor) -> torch.Tensor:
 class DecoderLayer(torch.nn.Module):
     def __init__(self, dim: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs", glue: str | None = None,
                  causal: bool = True, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
-                 dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16"):
+                 dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", qk_norm: bool = False,
+                 qk_norm_eps: float = 1e-6):
         super().__init__()
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', not {backend!r}")
@@ -66,6 +71,9 @@ class DecoderLayer(torch.nn.Module):
         self.backend, self.glue, self.dim, self.inter, self.linear = backend, glue, dim, inter, linear
         self.heads, self.kv_heads = heads, kv_heads
         self.head_dim, self.causal, self.rope_theta, self.eps = dim // heads, causal, rope_theta, eps
+        self.qk_norm, self.qk_norm_eps = bool(qk_norm), qk_norm_eps
+        if self.qk_norm and self.head_dim != 128:
+            raise ValueError("qk_norm takes head_dim 128")
         if backend == "kgs" and (self.head_dim != 128 or dtype != torch.bfloat16):
             raise ValueError("the kgs backend takes head_dim 128 and bf16")
         if glue == "kgs" and (dim % 512 or dim > 8192 or inter % 8):
@@ -93,6 +101,9 @@ class DecoderLayer(torch.nn.Module):
         self.qkv, self.o = lin(dim, wqkv), lin(dim, dim)
         self.mlp_norm = torch.nn.Parameter(torch.ones(dim, device=device, dtype=dtype))
         self.gate_up, self.down = lin(dim, 2 * inter), lin(inter, dim)
+        if self.qk_norm:  # registered last: the layer without them keeps its parameter order
+            self.q_norm = torch.nn.Parameter(torch.ones(self.head_dim, device=device, dtype=dtype))
+            self.k_norm = torch.nn.Parameter(torch.ones(self.head_dim, device=device, dtype=dtype))
         g = torch.Generator(device="cpu").manual_seed(seed)
         with torch.no_grad():  # identical init for both backends
             for m in (self.qkv, self.o, self.gate_up, self.down):
@@ -120,13 +131,22 @@ class DecoderLayer(torch.nn.Module):
 
             res, h = rmsnorm_residual(x2, d2, self.attn_norm, self.eps)
             cos, sin = self._rope_tables(s, x.device)
-            qkv = rope_qkv(self.qkv(h), cos, sin, nh + nkv, hd, s)
+            if self.qk_norm:
+                from kgs.ops.qknorm_rope import qknorm_rope
+
+                qkv = qknorm_rope(self.qkv(h), self.q_norm, self.k_norm, cos, sin, nh, nkv, s, eps=self.qk_norm_eps)
+            else:
+                qkv = rope_qkv(self.qkv(h), cos, sin, nh + nkv, hd, s)
             att = self.o(flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal))
             res, h = rmsnorm_residual(res, att, self.mlp_norm, self.eps)
             out = self.down(swiglu(self.gate_up(h)))
             return res.reshape(b, s, self.dim), out.reshape(b, s, self.dim)
         res = x2 if d2 is None else x2 + d2
-        qkv = _rope(self.qkv(_torch_rmsnorm(res, self.attn_norm, self.eps)), b, s, nh + nkv, hd, self.rope_theta)
+        qkv = self.qkv(_torch_rmsnorm(res, self.attn_norm, self.eps))
+        if self.qk_norm:
+            qkv = _qknorm_rope(qkv, self.q_norm, self.k_norm, s, nh, nkv, self.rope_theta, self.qk_norm_eps)
+        else:
+            qkv = _rope(qkv, b, s, nh + nkv, hd, self.rope_theta)
         if self.backend == "kgs":
             from kgs.ops.transformer import flash_attention_qkv
 
@@ -158,7 +178,7 @@ class DecoderLM(torch.nn.Module):
     def __init__(self, vocab: int, dim: int, layers: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs",
                  glue: str | None = None, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", embedding: str = "torch",
-                 tie_embeddings: bool = False):
+                 tie_embeddings: bool = False, qk_norm: bool = False, qk_norm_eps: float = 1e-6):
         super().__init__()
         if linear not in ("bf16", "fp8"):
             raise ValueError(f"linear must be 'bf16' or 'fp8', not {linear!r}")
@@ -170,7 +190,8 @@ class DecoderLM(torch.nn.Module):
         self.embedding, self.tie_embeddings = embedding, bool(tie_embeddings)
         self.layers = torch.nn.ModuleList(
             DecoderLayer(dim, heads, kv_heads, inter, backend=backend, glue=glue, rope_theta=rope_theta, eps=eps,
-                         device=device, dtype=dtype, seed=seed + 1 + i, linear=linear) for i in range(layers))
+                         device=device, dtype=dtype, seed=seed + 1 + i, linear=linear, qk_norm=qk_norm,
+                         qk_norm_eps=qk_norm_eps) for i in range(layers))
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:
             raise ValueError("the kgs loss takes a vocabulary that is a multiple of 8")

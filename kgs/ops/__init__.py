@@ -24,6 +24,9 @@
 * :func:`embedding`, :class:`Embedding`, :func:`embedding_rows`, :func:`embedding_rows_backward` --
   a trainable token embedding: a row gather and a deterministic dense scatter-sum
   (``native/kernels/embedding.hip``)
+* :func:`qknorm_rope`, :func:`qknorm_rope_`, :func:`qknorm_rope_backward`, :func:`ref_qknorm_rope`,
+  :func:`ref_qknorm_rope_backward` -- QK-norm (a per-head RMSNorm of q and k) fused with RoPE,
+  forward and backward with a deterministic dwq / dwk (``native/kernels/qknorm_rope.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -67,4 +70,11 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         # the op `embedding` shares its name with its module: the module is callable as the op
         mod = importlib.import_module(".embedding", __name__)
         return mod if name == "embedding" else getattr(mod, name)
+    if name in ("qknorm_rope", "qknorm_rope_", "qknorm_rope_backward", "ref_qknorm_rope",
+                "ref_qknorm_rope_backward"):
+        import importlib
+
+        # as `embedding`: the op shares its name with its module, which is callable as the op
+        mod = importlib.import_module(".qknorm_rope", __name__)
+        return mod if name == "qknorm_rope" else getattr(mod, name)
     raise AttributeError(name)

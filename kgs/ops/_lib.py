@@ -93,6 +93,12 @@ _SIGS = {
     "kgs_embed_fwd_bf16": ([_c_void_p] * 3 + [_c_int] * 3 + [_c_long, _c_long, ctypes.c_float, _c_void_p], _c_int),
     "kgs_embed_bwd_bf16": ([_c_void_p] * 4 + [_c_int] * 3 + [_c_long, _c_long, ctypes.c_float, _c_long, _c_void_p],
                            _c_int),
+    # QK-norm fused with RoPE (native/kernels/qknorm_rope.hip)
+    "kgs_qknorm_rope_bwd_workspace": ([_c_long, _c_int, _c_int], _c_long),
+    "kgs_qknorm_rope_fwd_bf16": ([_c_void_p] * 7 + [_c_long] + [_c_int] * 3 + [_c_long] * 2 + [_c_int] * 2 +
+                                 [ctypes.c_float, _c_int, _c_void_p], _c_int),
+    "kgs_qknorm_rope_bwd_bf16": ([_c_void_p] * 11 + [_c_long] + [_c_int] * 3 + [_c_long] * 3 + [_c_int] * 2 +
+                                 [ctypes.c_float, _c_int, _c_void_p], _c_int),
     # fp8 training producers (native/kernels/fp8_train.hip)
     "kgs_fp8_amax_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4, _c_int),
     "kgs_fp8_quant_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4 +
