@@ -57,8 +57,8 @@ class AttentionBlock(torch.nn.Module):
         self.qk_norm, self.qk_norm_eps = bool(qk_norm), qk_norm_eps
         if self.qk_norm and self.head_dim != 128:
             raise ValueError("qk_norm takes head_dim 128")
-        if backend == "kgs" and (self.head_dim != 128 or dtype != torch.bfloat16):
-            raise ValueError("the kgs backend takes head_dim 128 and bf16")
+        if backend == "kgs" and (self.head_dim not in (64, 128) or dtype != torch.bfloat16):
+            raise ValueError("the kgs backend takes head_dim 64 or 128 and bf16")
         wqkv = (heads + 2 * kv_heads) * self.head_dim
         if backend == "kgs":
             from kgs.ops.gemm import Linear
@@ -88,7 +88,7 @@ class AttentionBlock(torch.nn.Module):
         if self.backend == "kgs":
             from kgs.ops.transformer import flash_attention_qkv
 
-            a = flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal)
+            a = flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd)
         else:
             q = qkv[:, :nh * hd].reshape(b, s, nh, hd).transpose(1, 2)
             k = qkv[:, nh * hd:(nh + nkv) * hd].reshape(b, s, nkv, hd).transpose(1, 2)

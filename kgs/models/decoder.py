@@ -74,8 +74,8 @@ class DecoderLayer(torch.nn.Module):
         self.qk_norm, self.qk_norm_eps = bool(qk_norm), qk_norm_eps
         if self.qk_norm and self.head_dim != 128:
             raise ValueError("qk_norm takes head_dim 128")
-        if backend == "kgs" and (self.head_dim != 128 or dtype != torch.bfloat16):
-            raise ValueError("the kgs backend takes head_dim 128 and bf16")
+        if backend == "kgs" and (self.head_dim not in (64, 128) or dtype != torch.bfloat16):
+            raise ValueError("the kgs backend takes head_dim 64 or 128 and bf16")
         if glue == "kgs" and (dim % 512 or dim > 8192 or inter % 8):
             raise ValueError("the kgs glue takes dim a multiple of 512 up to 8192 and inter a multiple of 8")
         wqkv = (heads + 2 * kv_heads) * self.head_dim
@@ -137,7 +137,7 @@ class DecoderLayer(torch.nn.Module):
                 qkv = qknorm_rope(self.qkv(h), self.q_norm, self.k_norm, cos, sin, nh, nkv, s, eps=self.qk_norm_eps)
             else:
                 qkv = rope_qkv(self.qkv(h), cos, sin, nh + nkv, hd, s)
-            att = self.o(flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal))
+            att = self.o(flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd))
             res, h = rmsnorm_residual(res, att, self.mlp_norm, self.eps)
             out = self.down(swiglu(self.gate_up(h)))
             return res.reshape(b, s, self.dim), out.reshape(b, s, self.dim)
@@ -150,7 +150,7 @@ class DecoderLayer(torch.nn.Module):
         if self.backend == "kgs":
             from kgs.ops.transformer import flash_attention_qkv
 
-            a = flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal)
+            a = flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd)
         else:
             q = qkv[:, :nh * hd].reshape(b, s, nh, hd).transpose(1, 2)
             k = qkv[:, nh * hd:(nh + nkv) * hd].reshape(b, s, nkv, hd).transpose(1, 2)

@@ -10,7 +10,7 @@ tests compare them with.
 * :func:`add_rmsnorm_fp8`, :func:`silu_mul_fp8`, :func:`quantize_rows_fp8` -- the
   same producers emitting e4m3 rows + per-row scales for
   :func:`kgs.ops.gemm.gemm_fp8_rows` (W8A8, per-token dynamic activation scales)
-* :func:`attention_qkv` -- causal/full GQA flash attention (head_dim 128) reading
+* :func:`attention_qkv` -- causal/full GQA flash attention (head_dim 128, or 64 with ``seq % 128 == 0``) reading
   q, k, v straight out of the fused QKV buffer and writing ``[tokens, H*128]``
 * :func:`attention_qkv_lse`, :func:`attention_qkv_backward`, :func:`flash_attention_qkv`
   -- the same attention for training: the forward that keeps the log-sum-exp, the
@@ -586,6 +586,13 @@ def attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads:
     ld = qkv.stride(0)
     esz = qkv.element_size()
     base = qkv.data_ptr()
+    if head_dim == 64:  # native/kernels/attention_d64.hip; no lse wanted
+        rc = _lib.lib().kgs_attn64_fwd_bf16(base, base + heads * 64 * esz, base + (heads + kv_heads) * 64 * esz,
+                                            out.data_ptr(), None, batch, seq, heads, kv_heads, ld, ld, ld,
+                                            out.stride(0), float(scale), 1 if causal else 0,
+                                            _lib.stream_handle(qkv.device))
+        _lib.check(rc, "attention")
+        return out
     rc = _lib.lib().kgs_attn_fwd_bf16(base, base + heads * head_dim * esz, base + (heads + kv_heads) * head_dim * esz,
                                       out.data_ptr(), batch, seq, heads, kv_heads, head_dim, ld, ld, ld, out.stride(0),
                                       float(scale), 1 if causal else 0, _lib.stream_handle(qkv.device))
@@ -604,8 +611,8 @@ def _bf16_rows(t: torch.Tensor, name: str, rows: int, cols: int) -> None:
 
 
 def _attn_check(qkv, batch, seq, heads, kv_heads, head_dim):
-    if head_dim != 128:
-        raise ValueError("the training attention kernels take head_dim 128")
+    if head_dim not in (64, 128):
+        raise ValueError("the training attention kernels take head_dim 64 or 128")
     if heads <= 0 or kv_heads <= 0 or heads % kv_heads:
         raise ValueError("heads must be a positive multiple of kv_heads")
     if batch <= 0 or seq <= 0 or seq % 128:
@@ -626,6 +633,13 @@ def attention_qkv_lse(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_he
     lse = torch.empty((batch * heads, seq), dtype=torch.float32, device=qkv.device)
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     ld, esz, base = qkv.stride(0), qkv.element_size(), qkv.data_ptr()
+    if head_dim == 64:
+        rc = _lib.lib().kgs_attn64_fwd_bf16(base, base + heads * 64 * esz, base + (heads + kv_heads) * 64 * esz,
+                                            out.data_ptr(), lse.data_ptr(), batch, seq, heads, kv_heads, ld, ld, ld,
+                                            out.stride(0), float(scale), 1 if causal else 0,
+                                            _lib.stream_handle(qkv.device))
+        _lib.check(rc, "attention_qkv_lse")
+        return out, lse
     rc = _lib.lib().kgs_attn_fwd_lse_bf16(base, base + heads * head_dim * esz,
                                           base + (heads + kv_heads) * head_dim * esz, out.data_ptr(), lse.data_ptr(),
                                           batch, seq, heads, kv_heads, head_dim, ld, ld, ld, out.stride(0),
@@ -638,9 +652,9 @@ def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Ten
                            seq: int, heads: int, kv_heads: int, causal: bool = True, scale: float | None = None,
                            dqkv: torch.Tensor | None = None, head_dim: int = 128, _stages: int = 7) -> torch.Tensor:
     """Gradients of :func:`attention_qkv_lse` with respect to ``qkv`` from the
-    output's gradient ``dout`` (bf16 ``[batch*seq, >= heads*128]``, any row
+    output's gradient ``dout`` (bf16 ``[batch*seq, >= heads*head_dim]``, any row
     stride), in the fused layout: ``dqkv`` bf16 ``[batch*seq, >= (heads +
-    2*kv_heads)*128]`` holds dq, dk and dv as its three column groups (only those
+    2*kv_heads)*head_dim]`` holds dq, dk and dv as its three column groups (only those
     columns are written), so the QKV projection's backward consumes it with no
     ``cat``. Three launches (delta, dK/dV, dQ), no atomics: bitwise reproducible."""
     t, qc, w = batch * seq, heads * head_dim, (heads + 2 * kv_heads) * head_dim
@@ -665,6 +679,14 @@ def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Ten
     ld, esz, base = qkv.stride(0), qkv.element_size(), qkv.data_ptr()
     dld, dbase = dqkv.stride(0), dqkv.data_ptr()
     ko, vo = heads * head_dim * esz, (heads + kv_heads) * head_dim * esz
+    if head_dim == 64:
+        rc = _lib.lib().kgs_attn64_bwd_bf16_ex(base, base + ko, base + vo, out.data_ptr(), dout.data_ptr(),
+                                               lse.data_ptr(), dbase, dbase + ko, dbase + vo, ws.data_ptr(), batch,
+                                               seq, heads, kv_heads, ld, ld, ld, out.stride(0), dout.stride(0), dld,
+                                               dld, dld, float(scale), 1 if causal else 0, int(_stages),
+                                               _lib.stream_handle(qkv.device))
+        _lib.check(rc, "attention_qkv_backward")
+        return dqkv
     rc = _lib.lib().kgs_attn_bwd_bf16_ex(base, base + ko, base + vo, out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
                                          dbase, dbase + ko, dbase + vo, ws.data_ptr(), batch, seq, heads, kv_heads,
                                          head_dim, ld, ld, ld, out.stride(0), dout.stride(0), dld, dld, dld,
@@ -676,35 +698,36 @@ def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Ten
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, batch, seq, heads, kv_heads, causal, scale):
-        if not ctx.needs_input_grad[0]:
-            return attention_qkv(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale)  # inference: unchanged
-        out, lse = attention_qkv_lse(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale)
+    def forward(ctx, qkv, batch, seq, heads, kv_heads, causal, scale, head_dim=128):
+        if not ctx.needs_input_grad[0]:  # inference: unchanged
+            return attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale)
+        out, lse = attention_qkv_lse(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale, head_dim=head_dim)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.cfg = (batch, seq, heads, kv_heads, causal, scale)
+        ctx.cfg = (batch, seq, heads, kv_heads, causal, scale, head_dim)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        batch, seq, heads, kv_heads, causal, scale = ctx.cfg
+        batch, seq, heads, kv_heads, causal, scale, head_dim = ctx.cfg
         if dout.stride(1) != 1:
             dout = dout.contiguous()
-        dqkv = attention_qkv_backward(qkv, out, dout, lse, batch, seq, heads, kv_heads, causal=causal, scale=scale)
+        dqkv = attention_qkv_backward(qkv, out, dout, lse, batch, seq, heads, kv_heads, causal=causal, scale=scale,
+                                      head_dim=head_dim)
         if qkv.shape[1] != dqkv.shape[1]:  # a qkv wider than its three groups: the rest has no gradient
             full = torch.zeros_like(qkv)
             full[:, :dqkv.shape[1]] = dqkv
             dqkv = full
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def flash_attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads: int, causal: bool = True,
-                        scale: float | None = None) -> torch.Tensor:
-    """Differentiable :func:`attention_qkv` (head_dim 128, ``seq % 128 == 0``):
+                        scale: float | None = None, head_dim: int = 128) -> torch.Tensor:
+    """Differentiable :func:`attention_qkv` (head_dim 64 or 128, ``seq % 128 == 0``):
     forward and backward on the HIP kernels. When ``qkv`` needs no gradient this
     IS :func:`attention_qkv` (nothing saved)."""
-    _attn_check(qkv, batch, seq, heads, kv_heads, 128)
-    return _FlashAttnFn.apply(qkv, batch, seq, heads, kv_heads, causal, scale)
+    _attn_check(qkv, batch, seq, heads, kv_heads, head_dim)
+    return _FlashAttnFn.apply(qkv, batch, seq, heads, kv_heads, causal, scale, head_dim)
 
 
 # ----------------------------------------------------------------------------
