@@ -32,7 +32,13 @@ the embedding's one Parameter, as the small Llama-3.2 models have it.
 Parameters ``[128]`` and normalises each head of q and of k before the rotation:
 with the kgs glue on :func:`kgs.ops.qknorm_rope` in place of :func:`kgs.ops.rope_qkv`,
 otherwise in torch ops in fp32; off, the layer is exactly the one without the
-option. The reference has no model code; nothing here is ported.
+option. ``window=W`` (Mistral, Gemma-2/3, gpt-oss) makes the layer's attention causal
+sliding-window attention, each query seeing ``W`` keys counting itself: the kgs
+backend on the kernels of ``native/kernels/attention_window.hip`` (head_dim 128),
+the torch backend with the same mask given densely; ``DecoderLM(window=W,
+global_every=n)`` leaves every ``n``-th layer (``(i + 1) % n == 0``; Gemma-3 has 6)
+without the window, and ``window=None`` is exactly the model without the option.
+The reference has no model code; nothing here is ported.
 """
 from __future__ import annotations
 
@@ -57,7 +63,7 @@ class DecoderLayer(torch.nn.Module):
     def __init__(self, dim: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs", glue: str | None = None,
                  causal: bool = True, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", qk_norm: bool = False,
-                 qk_norm_eps: float = 1e-6):
+                 qk_norm_eps: float = 1e-6, window: int | None = None):
         super().__init__()
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', not {backend!r}")
@@ -76,6 +82,13 @@ class DecoderLayer(torch.nn.Module):
             raise ValueError("qk_norm takes head_dim 128")
         if backend == "kgs" and (self.head_dim not in (64, 128) or dtype != torch.bfloat16):
             raise ValueError("the kgs backend takes head_dim 64 or 128 and bf16")
+        if window is not None and window < 1:
+            raise ValueError("window must be at least 1")
+        if window is not None and not causal:
+            raise ValueError("window needs causal=True")
+        if window is not None and backend == "kgs" and self.head_dim != 128:
+            raise ValueError("the kgs backend with a window takes head_dim 128")
+        self.window = window
         if glue == "kgs" and (dim % 512 or dim > 8192 or inter % 8):
             raise ValueError("the kgs glue takes dim a multiple of 512 up to 8192 and inter a multiple of 8")
         wqkv = (heads + 2 * kv_heads) * self.head_dim
@@ -137,7 +150,8 @@ class DecoderLayer(torch.nn.Module):
                 qkv = qknorm_rope(self.qkv(h), self.q_norm, self.k_norm, cos, sin, nh, nkv, s, eps=self.qk_norm_eps)
             else:
                 qkv = rope_qkv(self.qkv(h), cos, sin, nh + nkv, hd, s)
-            att = self.o(flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd))
+            att = self.o(flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd,
+                                             window=self.window))
             res, h = rmsnorm_residual(res, att, self.mlp_norm, self.eps)
             out = self.down(swiglu(self.gate_up(h)))
             return res.reshape(b, s, self.dim), out.reshape(b, s, self.dim)
@@ -150,13 +164,19 @@ class DecoderLayer(torch.nn.Module):
         if self.backend == "kgs":
             from kgs.ops.transformer import flash_attention_qkv
 
-            a = flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd)
+            a = flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd, window=self.window)
         else:
             q = qkv[:, :nh * hd].reshape(b, s, nh, hd).transpose(1, 2)
             k = qkv[:, nh * hd:(nh + nkv) * hd].reshape(b, s, nkv, hd).transpose(1, 2)
             v = qkv[:, (nh + nkv) * hd:].reshape(b, s, nkv, hd).transpose(1, 2)
             k, v = (z.repeat_interleave(nh // nkv, dim=1) for z in (k, v))
-            a = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
+            if self.window is not None and self.window < s:
+                from kgs.ops.transformer import _window_mask
+
+                a = torch.nn.functional.scaled_dot_product_attention(
+                    q, k, v, attn_mask=_window_mask(s, self.window, x.device))
+            else:
+                a = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
             a = a.transpose(1, 2).reshape(t, nh * hd)
         res = res + self.o(a)
         out = self.down(_torch_swiglu(self.gate_up(_torch_rmsnorm(res, self.mlp_norm, self.eps))))
@@ -173,13 +193,18 @@ class DecoderLM(torch.nn.Module):
     parameter is ``embed.weight`` with the same seeded init either way.
     ``tie_embeddings``: ``head.weight`` IS ``embed.weight``, one Parameter that
     ``parameters()`` yields once (under ``embed.weight``); it takes the head's
-    init, ``randn * dim ** -0.5``, and its gradient is the sum of the two uses'."""
+    init, ``randn * dim ** -0.5``, and its gradient is the sum of the two uses'.
+    ``window``, ``global_every``: sliding-window attention on every layer but each
+    ``global_every``-th (0: on every layer), see the module docstring."""
 
     def __init__(self, vocab: int, dim: int, layers: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs",
                  glue: str | None = None, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", embedding: str = "torch",
-                 tie_embeddings: bool = False, qk_norm: bool = False, qk_norm_eps: float = 1e-6):
+                 tie_embeddings: bool = False, qk_norm: bool = False, qk_norm_eps: float = 1e-6,
+                 window: int | None = None, global_every: int = 0):
         super().__init__()
+        if global_every < 0:
+            raise ValueError("global_every must be 0 (no global layers) or a positive layer period")
         if linear not in ("bf16", "fp8"):
             raise ValueError(f"linear must be 'bf16' or 'fp8', not {linear!r}")
         if embedding not in ("torch", "kgs"):
@@ -191,7 +216,9 @@ class DecoderLM(torch.nn.Module):
         self.layers = torch.nn.ModuleList(
             DecoderLayer(dim, heads, kv_heads, inter, backend=backend, glue=glue, rope_theta=rope_theta, eps=eps,
                          device=device, dtype=dtype, seed=seed + 1 + i, linear=linear, qk_norm=qk_norm,
-                         qk_norm_eps=qk_norm_eps) for i in range(layers))
+                         qk_norm_eps=qk_norm_eps,
+                         window=None if global_every > 0 and (i + 1) % global_every == 0 else window)
+            for i in range(layers))
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:
             raise ValueError("the kgs loss takes a vocabulary that is a multiple of 8")

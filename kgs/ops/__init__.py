@@ -9,7 +9,9 @@
   ``native/kernels/attention.hip``)
 * :func:`flash_attention_qkv`, :func:`attention_qkv_lse`, :func:`attention_qkv_backward` --
   differentiable flash attention: forward with log-sum-exp and the dQ / dK / dV
-  kernels (``native/kernels/attention_train.hip``)
+  kernels (``native/kernels/attention_train.hip``); with ``window=W`` causal
+  sliding-window attention, ``W`` keys per query, whose work per query block is
+  bounded by ``W`` (``native/kernels/attention_window.hip``)
 * :func:`rmsnorm_residual`, :func:`swiglu`, :func:`rope_qkv`, :func:`softmax_cross_entropy` --
   the differentiable norm, SwiGLU, RoPE and LM loss, over :func:`rmsnorm_backward`,
   :func:`silu_mul_backward`, :func:`cross_entropy_rows` and

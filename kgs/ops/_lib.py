@@ -90,6 +90,13 @@ _SIGS = {
                             _c_int),
     "kgs_attn64_bwd_bf16_ex": ([_c_void_p] * 10 + [_c_int] * 4 + [_c_long] * 8 + [ctypes.c_float, _c_int, _c_int,
                                                                                    _c_void_p], _c_int),
+    # sliding-window training attention (native/kernels/attention_window.hip)
+    "kgs_attn_win_fwd_bf16": ([_c_void_p] * 5 + [_c_int] * 5 + [_c_long] * 4 + [ctypes.c_float, _c_int, _c_int,
+                                                                                 _c_void_p], _c_int),
+    "kgs_attn_win_bwd_bf16": ([_c_void_p] * 10 + [_c_int] * 5 + [_c_long] * 8 + [ctypes.c_float, _c_int, _c_int,
+                                                                                  _c_void_p], _c_int),
+    "kgs_attn_win_bwd_bf16_ex": ([_c_void_p] * 10 + [_c_int] * 5 + [_c_long] * 8 + [ctypes.c_float, _c_int, _c_int,
+                                                                                     _c_int, _c_void_p], _c_int),
     # training glue (native/kernels/train_ops.hip)
     "kgs_rmsnorm_bwd_workspace": ([_c_int, _c_int], _c_long),
     "kgs_rmsnorm_bwd_bf16": ([_c_void_p] * 7 + [_c_int, _c_int] + [_c_long] * 4 + [ctypes.c_float, _c_void_p], _c_int),

@@ -15,7 +15,8 @@ tests compare them with.
 * :func:`attention_qkv_lse`, :func:`attention_qkv_backward`, :func:`flash_attention_qkv`
   -- the same attention for training: the forward that keeps the log-sum-exp, the
   dQ / dK / dV kernels and the autograd op over them
-  (``native/kernels/attention_train.hip``)
+  (``native/kernels/attention_train.hip``); all of them take ``window=W`` for causal
+  sliding-window attention (``native/kernels/attention_window.hip``, head_dim 128)
 * :func:`rmsnorm_backward`, :func:`silu_mul_backward`, :func:`cross_entropy_rows`,
   :func:`cross_entropy_rows_backward` -- the backward kernels of the norm and of
   SwiGLU and the softmax cross-entropy over logit rows
@@ -573,9 +574,12 @@ def silu_mul(gu: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
 
 
 def attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads: int, head_dim: int = 128,
-                  causal: bool = True, scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+                  causal: bool = True, scale: float | None = None, out: torch.Tensor | None = None,
+                  window: int | None = None) -> torch.Tensor:
     """Flash attention over a fused QKV buffer ``[batch*seq, (heads + 2*kv_heads) * head_dim]``
-    (q heads, then k heads, then v heads per token). Returns ``[batch*seq, heads*head_dim]``."""
+    (q heads, then k heads, then v heads per token). Returns ``[batch*seq, heads*head_dim]``.
+    ``window=W`` (with ``causal``): query ``i`` sees the ``W`` keys ``max(0, i - W + 1) .. i``."""
+    window = _window(window, causal, seq, head_dim)
     _need(qkv, "qkv")
     if qkv.shape[0] != batch * seq or qkv.shape[1] < (heads + 2 * kv_heads) * head_dim:
         raise ValueError("qkv shape does not match batch/seq/heads")
@@ -586,6 +590,12 @@ def attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads:
     ld = qkv.stride(0)
     esz = qkv.element_size()
     base = qkv.data_ptr()
+    if window is not None:  # native/kernels/attention_window.hip; no lse wanted
+        rc = _lib.lib().kgs_attn_win_fwd_bf16(base, base + heads * 128 * esz, base + (heads + kv_heads) * 128 * esz,
+                                              out.data_ptr(), None, batch, seq, heads, kv_heads, 128, ld, ld, ld,
+                                              out.stride(0), float(scale), 1, window, _lib.stream_handle(qkv.device))
+        _lib.check(rc, "attention")
+        return out
     if head_dim == 64:  # native/kernels/attention_d64.hip; no lse wanted
         rc = _lib.lib().kgs_attn64_fwd_bf16(base, base + heads * 64 * esz, base + (heads + kv_heads) * 64 * esz,
                                             out.data_ptr(), None, batch, seq, heads, kv_heads, ld, ld, ld,
@@ -610,6 +620,22 @@ def _bf16_rows(t: torch.Tensor, name: str, rows: int, cols: int) -> None:
         raise ValueError(f"{name} shape does not match batch/seq/heads")
 
 
+def _window(window, causal, seq, head_dim):
+    """The window the kernels have to apply: ``None`` without one, and for one that
+    covers the sequence (``window >= seq`` IS plain causal attention)."""
+    if window is None:
+        return None
+    if window < 1:
+        raise ValueError("window must be at least 1")
+    if not causal:
+        raise ValueError("window needs causal=True")
+    if window >= seq:
+        return None
+    if head_dim != 128:
+        raise ValueError("a window shorter than seq takes head_dim 128")
+    return int(window)
+
+
 def _attn_check(qkv, batch, seq, heads, kv_heads, head_dim):
     if head_dim not in (64, 128):
         raise ValueError("the training attention kernels take head_dim 64 or 128")
@@ -624,15 +650,24 @@ def _attn_check(qkv, batch, seq, heads, kv_heads, head_dim):
 
 
 def attention_qkv_lse(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads: int, causal: bool = True,
-                      scale: float | None = None, head_dim: int = 128) -> tuple[torch.Tensor, torch.Tensor]:
+                      scale: float | None = None, head_dim: int = 128, window: int | None = None
+                      ) -> tuple[torch.Tensor, torch.Tensor]:
     """:func:`attention_qkv` (the same output bits) that also returns each query
     row's log-sum-exp of the scaled, masked scores: ``lse`` fp32 ``[batch*heads,
     seq]``, natural log -- what :func:`attention_qkv_backward` recomputes P from."""
+    window = _window(window, causal, seq, head_dim)
     _attn_check(qkv, batch, seq, heads, kv_heads, head_dim)
     out = torch.empty((batch * seq, heads * head_dim), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((batch * heads, seq), dtype=torch.float32, device=qkv.device)
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     ld, esz, base = qkv.stride(0), qkv.element_size(), qkv.data_ptr()
+    if window is not None:
+        rc = _lib.lib().kgs_attn_win_fwd_bf16(base, base + heads * 128 * esz, base + (heads + kv_heads) * 128 * esz,
+                                              out.data_ptr(), lse.data_ptr(), batch, seq, heads, kv_heads, 128, ld, ld,
+                                              ld, out.stride(0), float(scale), 1, window,
+                                              _lib.stream_handle(qkv.device))
+        _lib.check(rc, "attention_qkv_lse")
+        return out, lse
     if head_dim == 64:
         rc = _lib.lib().kgs_attn64_fwd_bf16(base, base + heads * 64 * esz, base + (heads + kv_heads) * 64 * esz,
                                             out.data_ptr(), lse.data_ptr(), batch, seq, heads, kv_heads, ld, ld, ld,
@@ -650,13 +685,16 @@ def attention_qkv_lse(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_he
 
 def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, batch: int,
                            seq: int, heads: int, kv_heads: int, causal: bool = True, scale: float | None = None,
-                           dqkv: torch.Tensor | None = None, head_dim: int = 128, _stages: int = 7) -> torch.Tensor:
+                           dqkv: torch.Tensor | None = None, head_dim: int = 128, _stages: int = 7,
+                           window: int | None = None) -> torch.Tensor:
     """Gradients of :func:`attention_qkv_lse` with respect to ``qkv`` from the
     output's gradient ``dout`` (bf16 ``[batch*seq, >= heads*head_dim]``, any row
     stride), in the fused layout: ``dqkv`` bf16 ``[batch*seq, >= (heads +
     2*kv_heads)*head_dim]`` holds dq, dk and dv as its three column groups (only those
     columns are written), so the QKV projection's backward consumes it with no
-    ``cat``. Three launches (delta, dK/dV, dQ), no atomics: bitwise reproducible."""
+    ``cat``. Three launches (delta, dK/dV, dQ), no atomics: bitwise reproducible.
+    ``window`` must be the forward's."""
+    window = _window(window, causal, seq, head_dim)
     t, qc, w = batch * seq, heads * head_dim, (heads + 2 * kv_heads) * head_dim
     for x, n in ((out, "out"), (dout, "dout")):
         _bf16_rows(x, n, t, qc)
@@ -679,6 +717,14 @@ def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Ten
     ld, esz, base = qkv.stride(0), qkv.element_size(), qkv.data_ptr()
     dld, dbase = dqkv.stride(0), dqkv.data_ptr()
     ko, vo = heads * head_dim * esz, (heads + kv_heads) * head_dim * esz
+    if window is not None:
+        rc = _lib.lib().kgs_attn_win_bwd_bf16_ex(base, base + ko, base + vo, out.data_ptr(), dout.data_ptr(),
+                                                 lse.data_ptr(), dbase, dbase + ko, dbase + vo, ws.data_ptr(), batch,
+                                                 seq, heads, kv_heads, 128, ld, ld, ld, out.stride(0), dout.stride(0),
+                                                 dld, dld, dld, float(scale), 1, window, int(_stages),
+                                                 _lib.stream_handle(qkv.device))
+        _lib.check(rc, "attention_qkv_backward")
+        return dqkv
     if head_dim == 64:
         rc = _lib.lib().kgs_attn64_bwd_bf16_ex(base, base + ko, base + vo, out.data_ptr(), dout.data_ptr(),
                                                lse.data_ptr(), dbase, dbase + ko, dbase + vo, ws.data_ptr(), batch,
@@ -698,36 +744,41 @@ def attention_qkv_backward(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Ten
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, batch, seq, heads, kv_heads, causal, scale, head_dim=128):
+    def forward(ctx, qkv, batch, seq, heads, kv_heads, causal, scale, head_dim=128, window=None):
         if not ctx.needs_input_grad[0]:  # inference: unchanged
-            return attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale)
-        out, lse = attention_qkv_lse(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale, head_dim=head_dim)
+            return attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale,
+                                 window=window)
+        out, lse = attention_qkv_lse(qkv, batch, seq, heads, kv_heads, causal=causal, scale=scale, head_dim=head_dim,
+                                     window=window)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.cfg = (batch, seq, heads, kv_heads, causal, scale, head_dim)
+        ctx.cfg = (batch, seq, heads, kv_heads, causal, scale, head_dim, window)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        batch, seq, heads, kv_heads, causal, scale, head_dim = ctx.cfg
+        batch, seq, heads, kv_heads, causal, scale, head_dim, window = ctx.cfg
         if dout.stride(1) != 1:
             dout = dout.contiguous()
         dqkv = attention_qkv_backward(qkv, out, dout, lse, batch, seq, heads, kv_heads, causal=causal, scale=scale,
-                                      head_dim=head_dim)
+                                      head_dim=head_dim, window=window)
         if qkv.shape[1] != dqkv.shape[1]:  # a qkv wider than its three groups: the rest has no gradient
             full = torch.zeros_like(qkv)
             full[:, :dqkv.shape[1]] = dqkv
             dqkv = full
-        return dqkv, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None
 
 
 def flash_attention_qkv(qkv: torch.Tensor, batch: int, seq: int, heads: int, kv_heads: int, causal: bool = True,
-                        scale: float | None = None, head_dim: int = 128) -> torch.Tensor:
+                        scale: float | None = None, head_dim: int = 128, window: int | None = None) -> torch.Tensor:
     """Differentiable :func:`attention_qkv` (head_dim 64 or 128, ``seq % 128 == 0``):
     forward and backward on the HIP kernels. When ``qkv`` needs no gradient this
-    IS :func:`attention_qkv` (nothing saved)."""
+    IS :func:`attention_qkv` (nothing saved). ``window=W`` (causal, head_dim 128) is
+    sliding-window attention, ``W`` keys per query counting itself, on the kernels
+    of ``native/kernels/attention_window.hip``; ``W >= seq`` is the causal op."""
+    window = _window(window, causal, seq, head_dim)
     _attn_check(qkv, batch, seq, heads, kv_heads, head_dim)
-    return _FlashAttnFn.apply(qkv, batch, seq, heads, kv_heads, causal, scale, head_dim)
+    return _FlashAttnFn.apply(qkv, batch, seq, heads, kv_heads, causal, scale, head_dim, window)
 
 
 # ----------------------------------------------------------------------------
@@ -1220,7 +1271,14 @@ def ref_silu_mul(gu):
     return (g * torch.sigmoid(g) * u).to(torch.bfloat16)
 
 
-def ref_attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=128, causal=True, scale=None):
+def _window_mask(seq: int, window: int, device=None) -> torch.Tensor:
+    """Boolean ``[seq, seq]``, true where query ``i`` sees key ``j``: ``0 <= i - j < window``."""
+    d = torch.arange(seq, device=device)[:, None] - torch.arange(seq, device=device)[None, :]
+    return (d >= 0) & (d < window)
+
+
+def ref_attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=128, causal=True, scale=None, window=None):
+    window = _window(window, causal, seq, 128)  # the reference itself takes any head_dim
     t = batch * seq
     q = qkv[:, :heads * head_dim].float().reshape(batch, seq, heads, head_dim).transpose(1, 2)
     k = qkv[:, heads * head_dim:(heads + kv_heads) * head_dim].float().reshape(batch, seq, kv_heads, head_dim)
@@ -1229,18 +1287,24 @@ def ref_attention_qkv(qkv, batch, seq, heads, kv_heads, head_dim=128, causal=Tru
     rep = heads // kv_heads
     k = k.transpose(1, 2).repeat_interleave(rep, dim=1)
     v = v.transpose(1, 2).repeat_interleave(rep, dim=1)
-    o = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale)
+    if window is not None:
+        o = torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=_window_mask(seq, window, qkv.device),
+                                                             scale=scale)
+    else:
+        o = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=scale)
     return o.transpose(1, 2).reshape(t, heads * head_dim)
 
 
-def ref_attention_qkv_backward(qkv, dout, batch, seq, heads, kv_heads, head_dim=128, causal=True, scale=None):
+def ref_attention_qkv_backward(qkv, dout, batch, seq, heads, kv_heads, head_dim=128, causal=True, scale=None,
+                               window=None):
     """fp32 reference of :func:`attention_qkv_backward` (CPU or GPU tensors):
     autograd through :func:`ref_attention_qkv` on an fp32 leaf. Returns the fp32
     gradient in the fused layout ``[batch*seq, (heads + 2*kv_heads) * head_dim]``."""
     w = (heads + 2 * kv_heads) * head_dim
     leaf = qkv[:, :w].detach().float().clone().requires_grad_(True)
     with torch.enable_grad():
-        o = ref_attention_qkv(leaf, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale)
+        o = ref_attention_qkv(leaf, batch, seq, heads, kv_heads, head_dim=head_dim, causal=causal, scale=scale,
+                              window=window)
     (g,) = torch.autograd.grad(o, leaf, dout[:, :heads * head_dim].detach().to(o.dtype))
     return g
 
