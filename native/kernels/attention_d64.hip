@@ -63,13 +63,22 @@
 //     dQ^T += K^T dS^T with dS^T straight from the accumulator; the forward's
 //     128-key tile and per-sub-block causal skip. No softmax couples the
 //     sub-blocks here, so each is finished before the next starts.
-#include "kgs_common.h"
+#include "attention_train.h"
 
 namespace kgs {
 namespace attn64 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x4s __attribute__((ext_vector_type(4)));
+using attn::bf16x4s;
+using attn::BwdArgs;
+using attn::dispatch_id;
+using attn::f32x16;
+using attn::FwdArgs;
+using attn::LOG2E;
+using attn::store_acc_row;
+using attn::tr_join;
+using attn::tr_wait;
+using attn::TrPair;
+// BwdArgs / FwdArgs::mask is the causal flag (0 / 1) in this file
 
 constexpr int HD = 64;
 constexpr int QB = 128;  // query rows per workgroup (4 waves x 32)
@@ -77,7 +86,7 @@ constexpr int KB = 128;  // rows per staged tile
 constexpr int TILE_BYTES = KB * HD * 2;  // 16 KB
 constexpr float NEG = -1.0e30f;
 constexpr float RESCALE = 8.0f;  // deferred-max threshold, log2 units: P <= 256
-constexpr float LOG2E = 1.4426950408889634f;
+static_assert(QB == attn::QB, "attention_train.h checks S against the 128 kernels' q-block");
 
 __device__ __forceinline__ int swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 __device__ __forceinline__ int off(int r, int c) { return 128 * r + 16 * (c ^ swz(r)); }
@@ -113,64 +122,10 @@ __device__ __forceinline__ bf16x8 tr_rows(const char* tile, int rb, int d, int l
   return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// The same fragment by inline-asm reads, for a loop that keeps an LDS-DMA in
-// flight (hipcc drains vector memory before a builtin transposed read). The
-// caller orders the DMA before these reads and retires them with tr_wait.
-struct TrPair {
-  bf16x4s lo, hi;
-};
+// The same fragment by asm reads (attention_train.h), for bwd_dkdv's loop
 __device__ __forceinline__ TrPair tr_rows_asm(const char* tile, int rb, int d, int lane) {
-  const unsigned a0 = (unsigned)(uintptr_t)(const KGS_LDS char*)(tile + tr_off(rb, d, lane, 0));
-  const unsigned a1 = (unsigned)(uintptr_t)(const KGS_LDS char*)(tile + tr_off(rb, d, lane, 1));
-  TrPair r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.lo) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.hi) : "v"(a1));
-  return r;
+  return attn::tr_read_asm(tile + tr_off(rb, d, lane, 0), tile + tr_off(rb, d, lane, 1));
 }
-// lgkmcnt(0) tied to the four fragments read above: every use of them depends
-// on this statement, so no consumer can be scheduled ahead of the wait
-__device__ __forceinline__ void tr_wait(TrPair (&f)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi),
-                 "+v"(f[3].lo), "+v"(f[3].hi));
-}
-__device__ __forceinline__ bf16x8 tr_join(const TrPair& f) {
-  return __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// acc (rows (r&3) + 8 (r>>2) + 4 hh of a 32-row block on the registers, the
-// lane's column on l32) x mul -> the 64 bf16 columns of the lane's row.
-__device__ __forceinline__ void store_acc_row(unsigned short* rowp, const f32x16 (&acc)[2], int hh, float mul) {
-#pragma unroll
-  for (int d = 0; d < 2; ++d)
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      uint2 pk;
-      pk.x = pack_bf16x2(acc[d][4 * r4 + 0] * mul, acc[d][4 * r4 + 1] * mul);
-      pk.y = pack_bf16x2(acc[d][4 * r4 + 2] * mul, acc[d][4 * r4 + 3] * mul);
-      *(uint2*)(rowp + 32 * d + 8 * r4 + 4 * hh) = pk;
-    }
-}
-
-// heaviest q-blocks first; 8 consecutive dispatch slots of one XCD take 4 heads
-// of one KV group, so the K/V tiles they share are L2 hits
-__device__ __forceinline__ int dispatch_id(int bid, int nwg) {
-  if (nwg & 31) return bid;
-  const int t = bid >> 3, x = bid & 7;
-  return ((t >> 2) << 5) | (x << 2) | (t & 3);
-}
-
-struct FwdArgs {
-  const unsigned short* q;
-  const unsigned short* k;
-  const unsigned short* v;
-  unsigned short* o;
-  float* lse;               // fp32 [B*H, S], natural log (LSE only)
-  long ldq, ldk, ldv, ldo;  // row strides (elements)
-  int B, S, H, HKV;
-  float sl2;  // softmax scale * log2(e)
-  int causal;
-};
 
 template <bool LSE>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void fwd(FwdArgs a) {
@@ -182,7 +137,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   const int lid = dispatch_id(blockIdx.x, gridDim.x);
   const int per = a.B * a.H;
   const int qi = lid / per, rem = lid - qi * per;
-  const int qb = a.causal ? nqb - 1 - qi : qi;
+  const int qb = a.mask ? nqb - 1 - qi : qi;
   const int b = rem / a.H, h = rem - b * a.H;
   const int kvh = h / (a.H / a.HKV);
 
@@ -204,7 +159,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     dma_tile(vbase + (long)jn * KB * a.ldv, a.ldv, smem[sb][1], w, lane);
   };
 
-  const int ntile = a.causal ? qb + 1 : a.S / KB;
+  const int ntile = a.mask ? qb + 1 : a.S / KB;
   dma_tiles(0, 0);
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the Q fragments and tile 0
   __syncthreads();
@@ -308,7 +263,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   // the causal diagonal tile is the last one: it runs after the loop, so the
   // loop body is straight-line code
-  const int nfull = a.causal ? qb : ntile;
+  const int nfull = a.mask ? qb : ntile;
   for (int j = 0; j < nfull; ++j) {
     const int buf = j & 1;
     // the other buffer was released by the previous tile's barrier
@@ -317,7 +272,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the next tile has landed
     __syncthreads();
   }
-  if (a.causal) tile(Flag<true>{}, w + 1, smem[nfull & 1][0], smem[nfull & 1][1]);
+  if (a.mask) tile(Flag<true>{}, w + 1, smem[nfull & 1][0], smem[nfull & 1][1]);
 
   l = xor32_sum(l);
   if constexpr (LSE) {
@@ -329,51 +284,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   store_acc_row(a.o + (tok0 + qrow) * a.ldo + (long)h * HD, o, hh, 1.0f / l);
 }
 
-struct BwdArgs {
-  const unsigned short* q;
-  const unsigned short* k;
-  const unsigned short* v;
-  const unsigned short* o;
-  const unsigned short* dout;
-  const float* lse;  // [B*H, S]
-  float* delta;      // [B*H, S] workspace
-  unsigned short* dq;
-  unsigned short* dk;
-  unsigned short* dv;
-  long ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;  // row strides (elements)
-  int B, S, H, HKV;
-  float scale, sl2;  // softmax scale, scale * log2(e)
-  int causal;
-};
-
-// delta[b H + h, s] = sum_d dO[b s, h, d] O[b s, h, d]: 8 lanes x 8 elements
-// per (token, head), summed in-lane and then by a fixed xor tree.
-__global__ __launch_bounds__(256) void bwd_prep(BwdArgs a) {
-  const long item = (long)blockIdx.x * 32 + (threadIdx.x >> 3);  // (token, head)
-  const long total = (long)a.B * a.S * a.H;
-  const int part = threadIdx.x & 7;
-  float acc = 0.f;
-  long tok = 0;
-  int h = 0;
-  if (item < total) {
-    tok = item / a.H;
-    h = (int)(item - tok * a.H);
-    const uint4 x = *(const uint4*)(a.o + tok * a.ldo + (long)h * HD + 8 * part);
-    const uint4 y = *(const uint4*)(a.dout + tok * a.lddo + (long)h * HD + 8 * part);
-    const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc = __builtin_fmaf(bf2f((unsigned short)(xs[i] & 0xffff)), bf2f((unsigned short)(ys[i] & 0xffff)), acc);
-      acc = __builtin_fmaf(bf2f((unsigned short)(xs[i] >> 16)), bf2f((unsigned short)(ys[i] >> 16)), acc);
-    }
-  }
-#pragma unroll
-  for (int s = 4; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 8);
-  if (item < total && part == 0) {
-    const long b = tok / a.S, srow = tok - b * a.S;
-    a.delta[(b * a.H + h) * a.S + srow] = acc;
-  }
-}
+__global__ __launch_bounds__(256) void bwd_prep(BwdArgs a) { attn::prep_body<HD>(a); }
 
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void bwd_dkdv(BwdArgs a) {
   // [buf][Q | dO (128 query rows each) | their lse | their delta]
@@ -405,7 +316,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   }
 
   const int nqt = a.S / KB;              // 128-row query tiles per head
-  const int qt0 = a.causal ? kbi : 0;    // first tile that sees this key block
+  const int qt0 = a.mask ? kbi : 0;      // first tile that sees this key block (mask: the causal flag)
   const int nper = nqt - qt0;
   const int niter = G * nper;
 
@@ -448,7 +359,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const char* Ls = smem[buf] + ROWS_OFF;
     // the diagonal tile holds the key block's own rows: sub-blocks before this
     // wave's keys see none of them, the wave's own sub-block is masked
-    const bool diag = a.causal && qc == 0;
+    const bool diag = a.mask && qc == 0;
     if (++qc == nper) qc = 0;
     const int t0 = diag ? w : 0;
 #pragma unroll
@@ -513,7 +424,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   // dS = scale P o (dP - delta): the scale is applied once, to the fp32 sum
   store_acc_row(a.dk + (tok0 + key) * a.lddk + (long)kvh * HD, dk, hh, a.scale);
-  store_acc_row(a.dv + (tok0 + key) * a.lddv + (long)kvh * HD, dv, hh, 1.0f);
+  store_acc_row(a.dv + (tok0 + key) * a.lddv + (long)kvh * HD, dv, hh);
 }
 
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void bwd_dq(BwdArgs a) {
@@ -525,7 +436,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   const int lid = dispatch_id(blockIdx.x, gridDim.x);  // the forward's order
   const int per = a.B * a.H;
   const int qi = lid / per, rem = lid - qi * per;
-  const int qb = a.causal ? nqb - 1 - qi : qi;
+  const int qb = a.mask ? nqb - 1 - qi : qi;
   const int b = rem / a.H, h = rem - b * a.H;
   const int kvh = h / (a.H / a.HKV);
 
@@ -554,7 +465,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     dma_tile(vbase + (long)jn * KB * a.ldv, a.ldv, smem[sb][1], w, lane);
   };
 
-  const int ntile = a.causal ? qb + 1 : a.S / KB;
+  const int ntile = a.mask ? qb + 1 : a.S / KB;
   dma_tiles(0, 0);
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the fragments, lse, delta and tile 0
   __syncthreads();
@@ -599,7 +510,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   };
 
   // the causal diagonal tile is the last one and runs after the loop
-  const int nfull = a.causal ? qb : ntile;
+  const int nfull = a.mask ? qb : ntile;
   for (int j = 0; j < nfull; ++j) {
     const int buf = j & 1;
     if (j + 1 < ntile) dma_tiles(j + 1, buf ^ 1);
@@ -607,7 +518,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the next tile has landed
     __syncthreads();
   }
-  if (a.causal) tile(Flag<true>{}, smem[nfull & 1][0], smem[nfull & 1][1]);
+  if (a.mask) tile(Flag<true>{}, smem[nfull & 1][0], smem[nfull & 1][1]);
 
   store_acc_row(a.dq + (tok0 + qrow) * a.lddq + (long)h * HD, dq, hh, a.scale);
 }
@@ -623,16 +534,11 @@ KGS_EXPORT int kgs_attn64_fwd_bf16(const void* q, const void* k, const void* v, 
                                   int HKV, long ldq, long ldk, long ldv, long ldo, float scale, int causal,
                                   hipStream_t s) {
   using namespace kgs::attn64;
-  if (B <= 0 || S <= 0 || H <= 0 || HKV <= 0 || H % HKV) return KGS_ERR_SHAPE;
-  if (S % QB) return KGS_ERR_SHAPE;
-  if (ldq < (long)H * HD || ldk < (long)HKV * HD || ldv < (long)HKV * HD || ldo < (long)H * HD) return KGS_ERR_SHAPE;
-  if (!q || !k || !v || !o) return KGS_ERR_ALIGN;
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)lse;
-  if ((al & 15) || (ldq | ldk | ldv | ldo) & 7) return KGS_ERR_ALIGN;
+  const FwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)o,
+                  (float*)lse, ldq, ldk, ldv, ldo, B, S, H, HKV, scale * LOG2E, causal ? 1 : 0};
+  // this entry has no head_dim argument: the hd check is given the kernels' own
+  if (const int err = kgs::attn::check_fwd(a, lse, false, HD, HD, 0)) return err;
   const long nwg = (long)B * H * (S / QB);
-  if (nwg > 0x7fffffff) return KGS_ERR_SHAPE;
-  FwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)o,
-            (float*)lse, ldq, ldk, ldv, ldo, B, S, H, HKV, scale * LOG2E, causal ? 1 : 0};
   if (lse)
     hipLaunchKernelGGL(fwd<true>, dim3((unsigned)nwg), dim3(256), 0, s, a);
   else
@@ -649,26 +555,13 @@ KGS_EXPORT int kgs_attn64_bwd_bf16_ex(const void* q, const void* k, const void* 
                                      int HKV, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
                                      long lddv, float scale, int causal, int stages, hipStream_t s) {
   using namespace kgs::attn64;
-  if (B <= 0 || S <= 0 || H <= 0 || HKV <= 0 || H % HKV) return KGS_ERR_SHAPE;
-  if (S % QB) return KGS_ERR_SHAPE;
-  const long qc = (long)H * HD, kc = (long)HKV * HD;
-  if (ldq < qc || ldo < qc || lddo < qc || lddq < qc || ldk < kc || ldv < kc || lddk < kc || lddv < kc)
-    return KGS_ERR_SHAPE;
-  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !ws) return KGS_ERR_ALIGN;
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)lse |
-                       (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)ws;
-  if ((al & 15) || (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) return KGS_ERR_ALIGN;
-  const long items = (long)B * S * H;
-  const long nprep = (items + 31) / 32, ndq = (long)B * H * (S / QB), nkv = (long)B * HKV * (S / KB);
-  if (nprep > 0x7fffffff) return KGS_ERR_SHAPE;
-  BwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (const unsigned short*)o,
-            (const unsigned short*)dout, (const float*)lse, (float*)ws, (unsigned short*)dq, (unsigned short*)dk,
-            (unsigned short*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B, S, H, HKV, scale,
-            scale * LOG2E, causal ? 1 : 0};
-  if (stages & 1) hipLaunchKernelGGL(bwd_prep, dim3((unsigned)nprep), dim3(256), 0, s, a);
-  if (stages & 2) hipLaunchKernelGGL(bwd_dkdv, dim3((unsigned)nkv), dim3(256), 0, s, a);
-  if (stages & 4) hipLaunchKernelGGL(bwd_dq, dim3((unsigned)ndq), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
+  const BwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v,
+                  (const unsigned short*)o, (const unsigned short*)dout, (const float*)lse, (float*)ws,
+                  (unsigned short*)dq, (unsigned short*)dk, (unsigned short*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk,
+                  lddv, B, S, H, HKV, scale, scale * LOG2E, causal ? 1 : 0};
+  // no head_dim argument here either
+  if (const int err = kgs::attn::check_bwd(a, HD, HD, 0)) return err;
+  return kgs::attn::launch_bwd(bwd_prep, bwd_dkdv, bwd_dq, a, HD, KB, stages, s);
 }
 
 KGS_EXPORT int kgs_attn64_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,

@@ -23,37 +23,46 @@
 //     over its query heads inside the workgroup. The KEY is on the MFMA lane
 //     (S = Q K^T, dP = dO V^T): the P and dS accumulators are the B operands of
 //     dV^T += dO^T P and dK^T += Q^T dS with no data movement. Q and dO tiles
-//     arrive by LDS-DMA in the forward's XOR image (attention_fwd.h), read by
-//     rows for S / dP and by ds_read_b64_tr_b16 for the transposed operands;
-//     the tile's lse and delta ride in the same DMA. A lone wave per SIMD
-//     cannot hide a drained DMA, so the transposed reads are inline asm behind
-//     the loop's own vmcnt + barrier and nothing inside a tile waits on vector
-//     memory (docs/architecture.md, "LDS-DMA alias waits").
-//     Causal: only query tiles at or after the key block are swept, waves
-//     skip tiles wholly before their keys, heaviest key blocks dispatch first.
+//     arrive by LDS-DMA in the forward's XOR image, read by rows for S / dP and
+//     by asm transposed reads for the transposed operands; the tile's lse and
+//     delta ride in the same DMA, so nothing inside a tile waits on vector
+//     memory. Causal: only query tiles at or after the key block are swept,
+//     waves skip tiles wholly before their keys, heaviest key blocks first.
 //   * bwd_dq: the mirror of the forward. One workgroup = 4 waves x 32 query
 //     rows of one (q-block, head), a lane owns one query row (lse and delta
 //     are lane scalars), S^T = K Q^T and dP^T = V dO^T with the Q and dO
 //     fragments in registers, dQ^T += K^T dS^T with dS^T straight from the
-//     accumulator and K^T by transposed reads. K/V double buffer by LDS-DMA,
-//     causal tiles skipped per wave, exactly as in the forward.
-#include "attention_fwd.h"
+//     accumulator and K^T by builtin transposed reads. K/V double buffer by
+//     LDS-DMA, causal tiles skipped per wave, exactly as in the forward.
+//
+// The mechanisms shared with attention_window.hip and attention_d64.hip (the
+// argument structs, the delta pass, the stores, the asm transposed reads, the
+// host-side checks and launches) are attention_train.h's, described there.
+// BwdArgs::mask is the causal flag here; both backward kernels read it where
+// they use it (a local copy changes bwd_dkdv's instruction stream).
+#include "attention_train.h"
 
 namespace kgs {
 namespace attn_train {
 
 using attn::Args;
+using attn::BwdArgs;
 using attn::f32x16;
 using attn::HD;
 using attn::KB;
+using attn::KBW;
+using attn::LOG2E;
 using attn::off;
 using attn::pack8;
 using attn::QB;
+using attn::store_acc_row;
 using attn::swz;
 using attn::TILE_BYTES;
-using attn::tr_frag;
-
-constexpr float LOG2E = 1.4426950408889634f;
+using attn::tr_join;
+using attn::tr_rows;
+using attn::tr_rows_asm;
+using attn::tr_wait;
+using attn::TrPair;
 
 struct LseArgs {
   Args a;
@@ -68,107 +77,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 #include "attention_fwd_body.h"
 }
 
-struct BwdArgs {
-  const unsigned short* q;
-  const unsigned short* k;
-  const unsigned short* v;
-  const unsigned short* o;
-  const unsigned short* dout;
-  const float* lse;  // [B*H, S]
-  float* delta;      // [B*H, S] workspace
-  unsigned short* dq;
-  unsigned short* dk;
-  unsigned short* dv;
-  long ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;  // row strides (elements)
-  int B, S, H, HKV;
-  float scale, sl2;  // softmax scale, scale * log2(e)
-  int causal;
-};
-
-// delta[b H + h, s] = sum_d dO[b s, h, d] O[b s, h, d]: 16 lanes x 8 elements
-// per (token, head), summed in-lane and then by a fixed xor tree.
-__global__ __launch_bounds__(256) void bwd_prep(BwdArgs a) {
-  const long item = (long)blockIdx.x * 16 + (threadIdx.x >> 4);  // (token, head)
-  const long total = (long)a.B * a.S * a.H;
-  const int part = threadIdx.x & 15;
-  float acc = 0.f;
-  long tok = 0;
-  int h = 0;
-  if (item < total) {
-    tok = item / a.H;
-    h = (int)(item - tok * a.H);
-    const uint4 x = *(const uint4*)(a.o + tok * a.ldo + (long)h * HD + 8 * part);
-    const uint4 y = *(const uint4*)(a.dout + tok * a.lddo + (long)h * HD + 8 * part);
-    const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc = __builtin_fmaf(bf2f((unsigned short)(xs[i] & 0xffff)), bf2f((unsigned short)(ys[i] & 0xffff)), acc);
-      acc = __builtin_fmaf(bf2f((unsigned short)(xs[i] >> 16)), bf2f((unsigned short)(ys[i] >> 16)), acc);
-    }
-  }
-#pragma unroll
-  for (int s = 8; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 16);
-  if (item < total && part == 0) {
-    const long b = tok / a.S, srow = tok - b * a.S;
-    a.delta[(b * a.H + h) * a.S + srow] = acc;
-  }
-}
-
-// acc (rows (r&3) + 8 (r>>2) + 4 hh of a 32-row block on the registers, the
-// lane's column on l32) -> 32 bf16 columns 32 d + ... of the lane's row.
-__device__ __forceinline__ void store_acc_row(unsigned short* rowp, const f32x16 (&acc)[4], int hh) {
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      uint2 pk;
-      pk.x = pack_bf16x2(acc[d][4 * r4 + 0], acc[d][4 * r4 + 1]);
-      pk.y = pack_bf16x2(acc[d][4 * r4 + 2], acc[d][4 * r4 + 3]);
-      *(uint2*)(rowp + 32 * d + 8 * r4 + 4 * hh) = pk;
-    }
-}
-
-// X^T fragments (A operand) of rows rb .. rb+15 x columns 32 d + l32 of a tile
-// in the XOR image, in the k order of an accumulator used as the B operand
-// (attention_fwd.h: row = rb + 8 (e>>2) + 4 hh + (e&3) for element e).
-__device__ __forceinline__ bf16x8 tr_rows(const char* tile, int rb, int d, int lane) {
-  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3, hh = lane >> 5;
-  const int c0 = 4 * d + 2 * (g & 1) + (tp >> 1);
-  const int row = rb + 4 * hh + tq;
-  return tr_frag(tile + off(row, c0) + 8 * (tp & 1), tile + off(row + 8, c0) + 8 * (tp & 1));
-}
-
-// The same fragment by inline-asm reads, for a loop that keeps an LDS-DMA in
-// flight: hipcc puts a vmcnt(0) before a BUILTIN ds_read_tr then (its LDS-DMA
-// alias check), which drains the DMA. The caller orders the DMA before these
-// reads (its own vmcnt + barrier) and retires them with tr_wait before use.
-struct TrPair {
-  attn::bf16x4s lo, hi;
-};
-__device__ __forceinline__ TrPair tr_rows_asm(const char* tile, int rb, int d, int lane) {
-  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3, hh = lane >> 5;
-  const int c0 = 4 * d + 2 * (g & 1) + (tp >> 1);
-  const int row = rb + 4 * hh + tq;
-  const unsigned a0 = (unsigned)(uintptr_t)(const KGS_LDS char*)(tile + off(row, c0) + 8 * (tp & 1));
-  const unsigned a1 = (unsigned)(uintptr_t)(const KGS_LDS char*)(tile + off(row + 8, c0) + 8 * (tp & 1));
-  TrPair r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.lo) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.hi) : "v"(a1));
-  return r;
-}
-// lgkmcnt(0) tied to the eight fragments read above: every use of them depends
-// on this statement, so no consumer can be scheduled ahead of the wait
-__device__ __forceinline__ void tr_wait(TrPair (&f)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi),
-                 "+v"(f[3].lo), "+v"(f[3].hi), "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi),
-                 "+v"(f[6].lo), "+v"(f[6].hi), "+v"(f[7].lo), "+v"(f[7].hi));
-}
-__device__ __forceinline__ bf16x8 tr_join(const TrPair& f) {
-  return __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-constexpr int KBW = 128;  // keys per bwd_dkdv workgroup (4 waves x 32)
+__global__ __launch_bounds__(256) void bwd_prep(BwdArgs a) { attn::prep_body<attn::HD>(a); }
 
 __global__ __launch_bounds__(256, 1) void bwd_dkdv(BwdArgs a) {
   // [buf][Q | dO (64 query rows each) | their lse | their delta | pad]
@@ -202,7 +111,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv(BwdArgs a) {
   }
 
   const int nqt = a.S / KB;                     // 64-row query tiles per head
-  const int qt0 = a.causal ? k0 / KB : 0;       // first tile that sees this key block
+  const int qt0 = a.mask ? k0 / KB : 0;         // first tile that sees this key block
   const int nper = nqt - qt0;
   const int niter = G * nper;
 
@@ -248,7 +157,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv(BwdArgs a) {
     const int q0 = qt * KB;
     // the other buffer was released by the previous iteration's barrier
     if (it + 1 < niter) dma_tiles(it + 1, buf ^ 1);
-    if (!a.causal || q0 + KB - 1 >= kw) {
+    if (!a.mask || q0 + KB - 1 >= kw) {
       const char* Qs = smem[buf];
       const char* Ds = smem[buf] + TILE_BYTES;
       const char* Ls = smem[buf] + ROWS_OFF;
@@ -268,7 +177,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv(BwdArgs a) {
           dp[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], dp[t], 0, 0, 0);
         }
       }
-      const bool diag = a.causal && q0 < kw + 31;
+      const bool diag = a.mask && q0 < kw + 31;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -329,7 +238,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   }
   const int per = a.B * a.H;
   const int qi = lid / per, rem = lid - qi * per;
-  const int qb = a.causal ? nqb - 1 - qi : qi;
+  const int qb = a.mask ? nqb - 1 - qi : qi;
   const int b = rem / a.H, h = rem - b * a.H;
   const int kvh = h / (a.H / a.HKV);
 
@@ -366,7 +275,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     }
   };
 
-  const int ntile = a.causal ? (q0 + QB) / KB : a.S / KB;
+  const int ntile = a.mask ? (q0 + QB) / KB : a.S / KB;
   dma_tiles(0, 0);
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the fragments, lse, delta and tile 0
   __syncthreads();
@@ -380,7 +289,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const int buf = j & 1;
     if (j + 1 < ntile) dma_tiles(j + 1, buf ^ 1);
     const int kv0 = j * KB;
-    if (!a.causal || kv0 <= qw + 31) {
+    if (!a.mask || kv0 <= qw + 31) {
       const char* Ks = smem[buf][0];
       const char* Vs = smem[buf][1];
       f32x16 s[2], dp[2];
@@ -399,7 +308,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
           dp[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dof[ks], dp[t], 0, 0, 0);
         }
       }
-      const bool diag = a.causal && kv0 + KB - 1 > qw;
+      const bool diag = a.mask && kv0 + KB - 1 > qw;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -435,18 +344,11 @@ KGS_EXPORT int kgs_attn_fwd_lse_bf16(const void* q, const void* k, const void* v
                                     int H, int HKV, int hd, long ldq, long ldk, long ldv, long ldo, float scale,
                                     int causal, hipStream_t s) {
   using namespace kgs::attn;
-  if (B <= 0 || S <= 0 || H <= 0 || HKV <= 0 || H % HKV) return KGS_ERR_SHAPE;
-  if (hd != HD || S % QB) return KGS_ERR_SHAPE;
-  if (ldq < (long)H * HD || ldk < (long)HKV * HD || ldv < (long)HKV * HD || ldo < (long)H * HD) return KGS_ERR_SHAPE;
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)lse;
-  if (!lse || (al & 15) || (ldq | ldk | ldv | ldo) & 7) return KGS_ERR_ALIGN;
-  const long nwg = (long)B * H * (S / QB);
-  if (nwg > 0x7fffffff) return KGS_ERR_SHAPE;
   kgs::attn_train::LseArgs p{{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v,
-                              (unsigned short*)o, ldq, ldk, ldv, ldo, B, S, H, HKV,
-                              scale * 1.4426950408889634f, causal ? 1 : 0, S, 0},
+                              (unsigned short*)o, ldq, ldk, ldv, ldo, B, S, H, HKV, scale * LOG2E, causal ? 1 : 0, S, 0},
                              (float*)lse};
-  hipLaunchKernelGGL(kgs::attn_train::fwd_lse, dim3((unsigned)nwg), dim3(256), 0, s, p);
+  if (const int err = check_fwd(p.a, lse, true, hd, HD, 0)) return err;
+  hipLaunchKernelGGL(kgs::attn_train::fwd_lse, dim3((unsigned)((long)B * H * (S / QB))), dim3(256), 0, s, p);
   return (int)hipGetLastError();
 }
 
@@ -460,26 +362,12 @@ KGS_EXPORT int kgs_attn_bwd_bf16_ex(const void* q, const void* k, const void* v,
                                    long lddk, long lddv, float scale, int causal, int stages, hipStream_t s) {
   using namespace kgs::attn;
   using namespace kgs::attn_train;
-  if (B <= 0 || S <= 0 || H <= 0 || HKV <= 0 || H % HKV) return KGS_ERR_SHAPE;
-  if (hd != HD || S % QB) return KGS_ERR_SHAPE;
-  const long qc = (long)H * HD, kc = (long)HKV * HD;
-  if (ldq < qc || ldo < qc || lddo < qc || lddq < qc || ldk < kc || ldv < kc || lddk < kc || lddv < kc)
-    return KGS_ERR_SHAPE;
-  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !ws) return KGS_ERR_ALIGN;
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)lse |
-                       (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)ws;
-  if ((al & 15) || (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) return KGS_ERR_ALIGN;
-  const long items = (long)B * S * H;
-  const long nprep = (items + 15) / 16, ndq = (long)B * H * (S / QB), nkv = (long)B * HKV * (S / KBW);
-  if (nprep > 0x7fffffff) return KGS_ERR_SHAPE;
-  BwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (const unsigned short*)o,
-            (const unsigned short*)dout, (const float*)lse, (float*)ws, (unsigned short*)dq, (unsigned short*)dk,
-            (unsigned short*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B, S, H, HKV, scale,
-            scale * LOG2E, causal ? 1 : 0};
-  if (stages & 1) hipLaunchKernelGGL(bwd_prep, dim3((unsigned)nprep), dim3(256), 0, s, a);
-  if (stages & 2) hipLaunchKernelGGL(bwd_dkdv, dim3((unsigned)nkv), dim3(256), 0, s, a);
-  if (stages & 4) hipLaunchKernelGGL(bwd_dq, dim3((unsigned)ndq), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
+  const BwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v,
+                  (const unsigned short*)o, (const unsigned short*)dout, (const float*)lse, (float*)ws,
+                  (unsigned short*)dq, (unsigned short*)dk, (unsigned short*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk,
+                  lddv, B, S, H, HKV, scale, scale * LOG2E, causal ? 1 : 0};
+  if (const int err = check_bwd(a, hd, HD, 0)) return err;
+  return launch_bwd(bwd_prep, bwd_dkdv, bwd_dq, a, HD, KBW, stages, s);
 }
 
 KGS_EXPORT int kgs_attn_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,

@@ -51,80 +51,37 @@
 // No atomics, no cross-workgroup waits, no memset: every sum has a fixed order
 // and the launches can be captured in a graph. The only workspace is the fp32
 // delta [B*H, S].
-#include "attention_fwd.h"
+#include "attention_train.h"
 
 namespace kgs {
 namespace attn_win {
 
+using attn::BwdArgs;
+using attn::dispatch_id;
+using attn::dma_pair;
 using attn::f32x16;
+using attn::FwdArgs;
 using attn::HD;
 using attn::KB;
+using attn::KBW;
+using attn::LOG2E;
 using attn::NEG;
 using attn::off;
 using attn::pack8;
 using attn::QB;
 using attn::RESCALE;
+using attn::store_acc_row;
 using attn::swz;
 using attn::TILE_BYTES;
 using attn::tr_frag;
-
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr int KBW = 128;  // keys per bwd_dkdv workgroup (4 waves x 32)
-
-struct FwdArgs {
-  const unsigned short* q;
-  const unsigned short* k;
-  const unsigned short* v;
-  unsigned short* o;
-  float* lse;               // fp32 [B*H, S], natural log (fwd<true> only)
-  long ldq, ldk, ldv, ldo;  // row strides (elements)
-  int B, S, H, HKV;
-  float sl2;  // softmax scale * log2(e)
-  int W;      // 1 <= W <= S
-};
-
-struct BwdArgs {
-  const unsigned short* q;
-  const unsigned short* k;
-  const unsigned short* v;
-  const unsigned short* o;
-  const unsigned short* dout;
-  const float* lse;  // [B*H, S]
-  float* delta;      // [B*H, S] workspace
-  unsigned short* dq;
-  unsigned short* dk;
-  unsigned short* dv;
-  long ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;  // row strides (elements)
-  int B, S, H, HKV;
-  float scale, sl2;  // softmax scale, scale * log2(e)
-  int W;             // 1 <= W <= S
-};
+using attn::tr_join;
+using attn::tr_rows;
+using attn::tr_rows_asm;
+using attn::tr_wait;
+using attn::TrPair;
 
 // (query i, key j) is outside the window or above the diagonal
 __device__ __forceinline__ bool hidden(int i, int j, int W) { return (unsigned)(i - j) >= (unsigned)W; }
-
-// The q-block's work item from its dispatch slot: ascending q-blocks, 8
-// consecutive slots of one XCD take 4 heads of one KV group.
-__device__ __forceinline__ int work_id(int bid, int nwg) {
-  if ((nwg & 31) != 0) return bid;
-  const int t = bid >> 3, x = bid & 7;
-  return ((t >> 2) << 5) | (x << 2) | (t & 3);
-}
-
-// K and V tile jt (64 keys) -> LDS [K | V] at sb by LDS-DMA: a 16 KB tile is 16
-// chunks of 1 KB = 4 rows of 256 B, wave w issues chunks 4w .. 4w+3 of each;
-// the lane landing at slot (r, c') of the XOR image fetches column c' ^ swz(r).
-__device__ __forceinline__ void dma_kv(const unsigned short* kbase, const unsigned short* vbase, long ldk, long ldv,
-                                       int jt, char* sb, int w, int lane) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int ch = 4 * w + i;
-    const int r = 4 * ch + (lane >> 4), c = (lane & 15) ^ swz(r);
-    const long row = (long)jt * KB + r;
-    glds16(kbase + row * ldk + 8 * c, sb + 1024 * ch);
-    glds16(vbase + row * ldv + 8 * c, sb + TILE_BYTES + 1024 * ch);
-  }
-}
 
 template <bool LSE>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void fwd(FwdArgs a) {
@@ -132,12 +89,12 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, hh = lane >> 5;
-  const int lid = work_id(blockIdx.x, gridDim.x);
+  const int lid = dispatch_id(blockIdx.x, gridDim.x);
   const int per = a.B * a.H;
   const int qb = lid / per, rem = lid - qb * per;
   const int b = rem / a.H, h = rem - b * a.H;
   const int kvh = h / (a.H / a.HKV);
-  const int W = a.W;
+  const int W = a.mask;
 
   const int q0 = qb * QB;
   const int qw = q0 + 32 * w;  // this wave's first query row
@@ -158,7 +115,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   const int jhi = (q0 + QB - 1) / KB;
   const int jlo = (q0 - W + 1 > 0 ? q0 - W + 1 : 0) / KB;
   const int ntile = jhi - jlo + 1;
-  dma_kv(kbase, vbase, a.ldk, a.ldv, jhi, smem[0], w, lane);
+  dma_pair(kbase, vbase, a.ldk, a.ldv, jhi, smem[0], w, lane);
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): Q fragments and the first tile
   __syncthreads();
 
@@ -172,7 +129,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   for (int j = 0; j < ntile; ++j) {
     const int buf = j & 1;
     // the other buffer was released by the previous tile's barrier
-    if (j + 1 < ntile) dma_kv(kbase, vbase, a.ldk, a.ldv, jhi - j - 1, smem[buf ^ 1], w, lane);
+    if (j + 1 < ntile) dma_pair(kbase, vbase, a.ldk, a.ldv, jhi - j - 1, smem[buf ^ 1], w, lane);
     const int kv0 = (jhi - j) * KB;
     // the tile meets [qw - W + 1, qw + 31]
     if (kv0 <= qw + 31 && kv0 + KB - 1 + W > qw) {
@@ -273,99 +230,10 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       a.lse[((long)b * a.H + h) * a.S + qrow] = (m * sl2 + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
   }
   const float inv = 1.0f / l;
-  unsigned short* op = a.o + (tok0 + qrow) * a.ldo + (long)h * HD;
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      uint2 pk;
-      pk.x = pack_bf16x2(o[d][4 * r4 + 0] * inv, o[d][4 * r4 + 1] * inv);
-      pk.y = pack_bf16x2(o[d][4 * r4 + 2] * inv, o[d][4 * r4 + 3] * inv);
-      *(uint2*)(op + 32 * d + 8 * r4 + 4 * hh) = pk;
-    }
+  store_acc_row(a.o + (tok0 + qrow) * a.ldo + (long)h * HD, o, hh, inv);
 }
 
-// delta[b H + h, s] = sum_d dO[b s, h, d] O[b s, h, d]: 16 lanes x 8 elements
-// per (token, head), summed in-lane and then by a fixed xor tree.
-__global__ __launch_bounds__(256) void bwd_prep(BwdArgs a) {
-  const long item = (long)blockIdx.x * 16 + (threadIdx.x >> 4);  // (token, head)
-  const long total = (long)a.B * a.S * a.H;
-  const int part = threadIdx.x & 15;
-  float acc = 0.f;
-  long tok = 0;
-  int h = 0;
-  if (item < total) {
-    tok = item / a.H;
-    h = (int)(item - tok * a.H);
-    const uint4 x = *(const uint4*)(a.o + tok * a.ldo + (long)h * HD + 8 * part);
-    const uint4 y = *(const uint4*)(a.dout + tok * a.lddo + (long)h * HD + 8 * part);
-    const unsigned xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      acc = __builtin_fmaf(bf2f((unsigned short)(xs[i] & 0xffff)), bf2f((unsigned short)(ys[i] & 0xffff)), acc);
-      acc = __builtin_fmaf(bf2f((unsigned short)(xs[i] >> 16)), bf2f((unsigned short)(ys[i] >> 16)), acc);
-    }
-  }
-#pragma unroll
-  for (int s = 8; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 16);
-  if (item < total && part == 0) {
-    const long b = tok / a.S, srow = tok - b * a.S;
-    a.delta[(b * a.H + h) * a.S + srow] = acc;
-  }
-}
-
-// acc (rows (r&3) + 8 (r>>2) + 4 hh of a 32-row block on the registers, the
-// lane's column on l32) -> 32 bf16 columns 32 d + ... of the lane's row.
-__device__ __forceinline__ void store_acc_row(unsigned short* rowp, const f32x16 (&acc)[4], int hh) {
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      uint2 pk;
-      pk.x = pack_bf16x2(acc[d][4 * r4 + 0], acc[d][4 * r4 + 1]);
-      pk.y = pack_bf16x2(acc[d][4 * r4 + 2], acc[d][4 * r4 + 3]);
-      *(uint2*)(rowp + 32 * d + 8 * r4 + 4 * hh) = pk;
-    }
-}
-
-// X^T fragments (A operand) of rows rb .. rb+15 x columns 32 d + l32 of a tile
-// in the XOR image, in the k order of an accumulator used as the B operand
-// (row = rb + 8 (e>>2) + 4 hh + (e&3) for element e).
-__device__ __forceinline__ bf16x8 tr_rows(const char* tile, int rb, int d, int lane) {
-  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3, hh = lane >> 5;
-  const int c0 = 4 * d + 2 * (g & 1) + (tp >> 1);
-  const int row = rb + 4 * hh + tq;
-  return tr_frag(tile + off(row, c0) + 8 * (tp & 1), tile + off(row + 8, c0) + 8 * (tp & 1));
-}
-
-// The same fragment by inline-asm reads, for bwd_dkdv's loop, which keeps an
-// LDS-DMA in flight with one wave per SIMD: hipcc drains vector memory before a
-// BUILTIN ds_read_tr there (its LDS-DMA alias check). The loop orders the DMA
-// before these reads itself (vmcnt + barrier) and retires them with tr_wait.
-struct TrPair {
-  attn::bf16x4s lo, hi;
-};
-__device__ __forceinline__ TrPair tr_rows_asm(const char* tile, int rb, int d, int lane) {
-  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3, hh = lane >> 5;
-  const int c0 = 4 * d + 2 * (g & 1) + (tp >> 1);
-  const int row = rb + 4 * hh + tq;
-  const unsigned a0 = (unsigned)(uintptr_t)(const KGS_LDS char*)(tile + off(row, c0) + 8 * (tp & 1));
-  const unsigned a1 = (unsigned)(uintptr_t)(const KGS_LDS char*)(tile + off(row + 8, c0) + 8 * (tp & 1));
-  TrPair r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.lo) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r.hi) : "v"(a1));
-  return r;
-}
-// lgkmcnt(0) tied to the eight fragments: no use of them is scheduled above it
-__device__ __forceinline__ void tr_wait(TrPair (&f)[8]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(f[0].lo), "+v"(f[0].hi), "+v"(f[1].lo), "+v"(f[1].hi), "+v"(f[2].lo), "+v"(f[2].hi),
-                 "+v"(f[3].lo), "+v"(f[3].hi), "+v"(f[4].lo), "+v"(f[4].hi), "+v"(f[5].lo), "+v"(f[5].hi),
-                 "+v"(f[6].lo), "+v"(f[6].hi), "+v"(f[7].lo), "+v"(f[7].hi));
-}
-__device__ __forceinline__ bf16x8 tr_join(const TrPair& f) {
-  return __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+__global__ __launch_bounds__(256) void bwd_prep(BwdArgs a) { attn::prep_body<HD>(a); }
 
 __global__ __launch_bounds__(256, 1) void bwd_dkdv(BwdArgs a) {
   // [buf][Q | dO (64 query rows each) | their lse | their delta | pad]
@@ -375,7 +243,7 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv(BwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, hh = lane >> 5;
   const int G = a.H / a.HKV;
-  const int W = a.W;
+  const int W = a.mask;
   // ascending key blocks: the last W / 128 blocks, whose sweep S clips, go last
   const int per = a.B * a.HKV;
   const int kbi = blockIdx.x / per, rem = blockIdx.x - kbi * per;
@@ -516,12 +384,12 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, hh = lane >> 5;
-  const int lid = work_id(blockIdx.x, gridDim.x);
+  const int lid = dispatch_id(blockIdx.x, gridDim.x);
   const int per = a.B * a.H;
   const int qb = lid / per, rem = lid - qb * per;
   const int b = rem / a.H, h = rem - b * a.H;
   const int kvh = h / (a.H / a.HKV);
-  const int W = a.W;
+  const int W = a.mask;
 
   const int q0 = qb * QB;
   const int qw = q0 + 32 * w;  // this wave's first query row
@@ -550,7 +418,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   const int jhi = (q0 + QB - 1) / KB;
   const int jlo = (q0 - W + 1 > 0 ? q0 - W + 1 : 0) / KB;
   const int ntile = jhi - jlo + 1;
-  dma_kv(kbase, vbase, a.ldk, a.ldv, jhi, smem[0], w, lane);
+  dma_pair(kbase, vbase, a.ldk, a.ldv, jhi, smem[0], w, lane);
   __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the fragments, lse, delta and the first tile
   __syncthreads();
 
@@ -561,7 +429,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   for (int j = 0; j < ntile; ++j) {
     const int buf = j & 1;
-    if (j + 1 < ntile) dma_kv(kbase, vbase, a.ldk, a.ldv, jhi - j - 1, smem[buf ^ 1], w, lane);
+    if (j + 1 < ntile) dma_pair(kbase, vbase, a.ldk, a.ldv, jhi - j - 1, smem[buf ^ 1], w, lane);
     const int kv0 = (jhi - j) * KB;
     if (kv0 <= qw + 31 && kv0 + KB - 1 + W > qw) {
       const char* Ks = smem[buf];
@@ -622,17 +490,11 @@ KGS_EXPORT int kgs_attn_win_fwd_bf16(const void* q, const void* k, const void* v
                                     int causal, int window, hipStream_t s) {
   using namespace kgs::attn;
   using namespace kgs::attn_win;
-  if (B <= 0 || S <= 0 || H <= 0 || HKV <= 0 || H % HKV || window < 1) return KGS_ERR_SHAPE;
-  if (hd != HD || S % QB) return KGS_ERR_SHAPE;
-  if (!causal) return KGS_ERR_ARG;
-  if (ldq < (long)H * HD || ldk < (long)HKV * HD || ldv < (long)HKV * HD || ldo < (long)H * HD) return KGS_ERR_SHAPE;
-  if (!q || !k || !v || !o) return KGS_ERR_ALIGN;
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)lse;
-  if ((al & 15) || (ldq | ldk | ldv | ldo) & 7) return KGS_ERR_ALIGN;
+  const FwdArgs p{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)o,
+                  (float*)lse, ldq, ldk, ldv, ldo, B, S, H, HKV, scale * LOG2E, window < S ? window : S};
+  if (const int err = check_fwd(p, lse, false, hd, HD, window < 1 ? KGS_ERR_SHAPE : !causal ? KGS_ERR_ARG : 0))
+    return err;
   const long nwg = (long)B * H * (S / QB);
-  if (nwg > 0x7fffffff) return KGS_ERR_SHAPE;
-  FwdArgs p{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)o,
-            (float*)lse, ldq, ldk, ldv, ldo, B, S, H, HKV, scale * LOG2E, window < S ? window : S};
   if (lse)
     hipLaunchKernelGGL(fwd<true>, dim3((unsigned)nwg), dim3(256), 0, s, p);
   else
@@ -650,27 +512,12 @@ KGS_EXPORT int kgs_attn_win_bwd_bf16_ex(const void* q, const void* k, const void
                                        hipStream_t s) {
   using namespace kgs::attn;
   using namespace kgs::attn_win;
-  if (B <= 0 || S <= 0 || H <= 0 || HKV <= 0 || H % HKV || window < 1) return KGS_ERR_SHAPE;
-  if (hd != HD || S % QB) return KGS_ERR_SHAPE;
-  if (!causal) return KGS_ERR_ARG;
-  const long qc = (long)H * HD, kc = (long)HKV * HD;
-  if (ldq < qc || ldo < qc || lddo < qc || lddq < qc || ldk < kc || ldv < kc || lddk < kc || lddv < kc)
-    return KGS_ERR_SHAPE;
-  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !ws) return KGS_ERR_ALIGN;
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o | (uintptr_t)dout | (uintptr_t)lse |
-                       (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)ws;
-  if ((al & 15) || (ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) return KGS_ERR_ALIGN;
-  const long items = (long)B * S * H;
-  const long nprep = (items + 15) / 16, ndq = (long)B * H * (S / QB), nkv = (long)B * HKV * (S / KBW);
-  if (nprep > 0x7fffffff) return KGS_ERR_SHAPE;
-  BwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (const unsigned short*)o,
-            (const unsigned short*)dout, (const float*)lse, (float*)ws, (unsigned short*)dq, (unsigned short*)dk,
-            (unsigned short*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, B, S, H, HKV, scale,
-            scale * LOG2E, window < S ? window : S};
-  if (stages & 1) hipLaunchKernelGGL(bwd_prep, dim3((unsigned)nprep), dim3(256), 0, s, a);
-  if (stages & 2) hipLaunchKernelGGL(bwd_dkdv, dim3((unsigned)nkv), dim3(256), 0, s, a);
-  if (stages & 4) hipLaunchKernelGGL(bwd_dq, dim3((unsigned)ndq), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
+  const BwdArgs a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v,
+                  (const unsigned short*)o, (const unsigned short*)dout, (const float*)lse, (float*)ws,
+                  (unsigned short*)dq, (unsigned short*)dk, (unsigned short*)dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk,
+                  lddv, B, S, H, HKV, scale, scale * LOG2E, window < S ? window : S};
+  if (const int err = check_bwd(a, hd, HD, window < 1 ? KGS_ERR_SHAPE : !causal ? KGS_ERR_ARG : 0)) return err;
+  return launch_bwd(bwd_prep, bwd_dkdv, bwd_dq, a, HD, KBW, stages, s);
 }
 
 KGS_EXPORT int kgs_attn_win_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,

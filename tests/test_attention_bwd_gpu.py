@@ -261,5 +261,9 @@ def test_raw_entry_rejects_bad_arguments_and_launches_nothing():
                                           ctypes.c_void_p(0), b, s, nh, nkv, HD, ld, ld, ld, ld, 0.1, 1,
                                           _lib.stream_handle(qkv.device))
     assert rc == -2                # null lse
+    rc = _lib.lib().kgs_attn_fwd_lse_bf16(ctypes.c_void_p(0), qkv.data_ptr() + ko, qkv.data_ptr() + vo, dqkv.data_ptr(),
+                                          ws.data_ptr(), b, s, nh, nkv, HD, ld, ld, ld, ld, 0.1, 1,
+                                          _lib.stream_handle(qkv.device))
+    assert rc == -2                # null q, like the head_dim 64 and window forwards
     torch.cuda.synchronize()
     assert (dqkv == poison).all() and (ws == poison).all()
