@@ -38,6 +38,11 @@ backend on the kernels of ``native/kernels/attention_window.hip`` (head_dim 128)
 the torch backend with the same mask given densely; ``DecoderLM(window=W,
 global_every=n)`` leaves every ``n``-th layer (``(i + 1) % n == 0``; Gemma-3 has 6)
 without the window, and ``window=None`` is exactly the model without the option.
+``experts=E`` (Mixtral, Qwen3-MoE, gpt-oss) gives the layer a mixture-of-experts FFN,
+``moe`` (:class:`kgs.models.moe.MoEFFN`: a router and ``E`` SwiGLU FFNs of width ``inter``,
+``top_k`` of them per token, on slabs of ``capacity_factor`` times the even share),
+in place of ``gate_up`` / ``down``: the kgs backend on the routing kernels of
+``native/kernels/moe_route.hip``; ``experts=0`` is exactly the dense layer.
 The reference has no model code; nothing here is ported.
 """
 from __future__ import annotations
@@ -63,7 +68,8 @@ class DecoderLayer(torch.nn.Module):
     def __init__(self, dim: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs", glue: str | None = None,
                  causal: bool = True, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", qk_norm: bool = False,
-                 qk_norm_eps: float = 1e-6, window: int | None = None):
+                 qk_norm_eps: float = 1e-6, window: int | None = None, experts: int = 0, top_k: int = 2,
+                 capacity_factor: float = 1.25):
         super().__init__()
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', not {backend!r}")
@@ -89,6 +95,11 @@ class DecoderLayer(torch.nn.Module):
         if window is not None and backend == "kgs" and self.head_dim != 128:
             raise ValueError("the kgs backend with a window takes head_dim 128")
         self.window = window
+        if experts < 0:
+            raise ValueError("experts must be 0 (a dense FFN) or the number of experts")
+        if experts and (linear != "bf16" or glue != backend):
+            raise ValueError("experts take linear='bf16' and the backend's own glue")
+        self.num_experts = experts
         if glue == "kgs" and (dim % 512 or dim > 8192 or inter % 8):
             raise ValueError("the kgs glue takes dim a multiple of 512 up to 8192 and inter a multiple of 8")
         wqkv = (heads + 2 * kv_heads) * self.head_dim
@@ -113,13 +124,19 @@ class DecoderLayer(torch.nn.Module):
         self.attn_norm = torch.nn.Parameter(torch.ones(dim, device=device, dtype=dtype))
         self.qkv, self.o = lin(dim, wqkv), lin(dim, dim)
         self.mlp_norm = torch.nn.Parameter(torch.ones(dim, device=device, dtype=dtype))
-        self.gate_up, self.down = lin(dim, 2 * inter), lin(inter, dim)
+        if experts:
+            from .moe import MoEFFN
+
+            self.moe = MoEFFN(dim, inter, experts, top_k=top_k, capacity_factor=capacity_factor, backend=backend,
+                              device=device, dtype=dtype, seed=seed)
+        else:
+            self.gate_up, self.down = lin(dim, 2 * inter), lin(inter, dim)
         if self.qk_norm:  # registered last: the layer without them keeps its parameter order
             self.q_norm = torch.nn.Parameter(torch.ones(self.head_dim, device=device, dtype=dtype))
             self.k_norm = torch.nn.Parameter(torch.ones(self.head_dim, device=device, dtype=dtype))
         g = torch.Generator(device="cpu").manual_seed(seed)
         with torch.no_grad():  # identical init for both backends
-            for m in (self.qkv, self.o, self.gate_up, self.down):
+            for m in (self.qkv, self.o) if experts else (self.qkv, self.o, self.gate_up, self.down):
                 m.weight.copy_(torch.randn(m.weight.shape, generator=g) * m.weight.shape[1] ** -0.5)
         self._tables = {}
 
@@ -153,7 +170,7 @@ class DecoderLayer(torch.nn.Module):
             att = self.o(flash_attention_qkv(qkv, b, s, nh, nkv, causal=self.causal, head_dim=hd,
                                              window=self.window))
             res, h = rmsnorm_residual(res, att, self.mlp_norm, self.eps)
-            out = self.down(swiglu(self.gate_up(h)))
+            out = self.moe(h) if self.num_experts else self.down(swiglu(self.gate_up(h)))
             return res.reshape(b, s, self.dim), out.reshape(b, s, self.dim)
         res = x2 if d2 is None else x2 + d2
         qkv = self.qkv(_torch_rmsnorm(res, self.attn_norm, self.eps))
@@ -179,7 +196,8 @@ class DecoderLayer(torch.nn.Module):
                 a = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=self.causal)
             a = a.transpose(1, 2).reshape(t, nh * hd)
         res = res + self.o(a)
-        out = self.down(_torch_swiglu(self.gate_up(_torch_rmsnorm(res, self.mlp_norm, self.eps))))
+        h = _torch_rmsnorm(res, self.mlp_norm, self.eps)
+        out = self.moe(h) if self.num_experts else self.down(_torch_swiglu(self.gate_up(h)))
         return res.reshape(b, s, self.dim), out.reshape(b, s, self.dim)
 
 
@@ -201,7 +219,8 @@ class DecoderLM(torch.nn.Module):
                  glue: str | None = None, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", embedding: str = "torch",
                  tie_embeddings: bool = False, qk_norm: bool = False, qk_norm_eps: float = 1e-6,
-                 window: int | None = None, global_every: int = 0):
+                 window: int | None = None, global_every: int = 0, experts: int = 0, top_k: int = 2,
+                 capacity_factor: float = 1.25):
         super().__init__()
         if global_every < 0:
             raise ValueError("global_every must be 0 (no global layers) or a positive layer period")
@@ -217,7 +236,8 @@ class DecoderLM(torch.nn.Module):
             DecoderLayer(dim, heads, kv_heads, inter, backend=backend, glue=glue, rope_theta=rope_theta, eps=eps,
                          device=device, dtype=dtype, seed=seed + 1 + i, linear=linear, qk_norm=qk_norm,
                          qk_norm_eps=qk_norm_eps,
-                         window=None if global_every > 0 and (i + 1) % global_every == 0 else window)
+                         window=None if global_every > 0 and (i + 1) % global_every == 0 else window,
+                         experts=experts, top_k=top_k, capacity_factor=capacity_factor)
             for i in range(layers))
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:

@@ -29,6 +29,10 @@
 * :func:`qknorm_rope`, :func:`qknorm_rope_`, :func:`qknorm_rope_backward`, :func:`ref_qknorm_rope`,
   :func:`ref_qknorm_rope_backward` -- QK-norm (a per-head RMSNorm of q and k) fused with RoPE,
   forward and backward with a deterministic dwq / dwk (``native/kernels/qknorm_rope.hip``)
+* :func:`moe_router`, :func:`moe_dispatch`, :func:`moe_combine` over :func:`moe_route`, :func:`moe_gather`,
+  :func:`moe_combine_backward`, :func:`moe_route_backward` -- mixture-of-experts routing: top-k
+  selection with softmax weights, fixed-capacity slots, the dispatch gather and the weighted
+  combine, forward and backward (``native/kernels/moe_route.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -79,4 +83,10 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         # as `embedding`: the op shares its name with its module, which is callable as the op
         mod = importlib.import_module(".qknorm_rope", __name__)
         return mod if name == "qknorm_rope" else getattr(mod, name)
+    if name in ("moe_route", "moe_route_backward", "moe_gather", "moe_combine", "moe_combine_backward", "moe_router",
+                "moe_dispatch", "Route", "ref_moe_route", "ref_moe_gather", "ref_moe_combine",
+                "ref_moe_dispatch_backward", "ref_moe_combine_backward", "ref_moe_route_backward"):
+        from . import moe
+
+        return getattr(moe, name)
     raise AttributeError(name)

@@ -113,6 +113,15 @@ _SIGS = {
                                  [ctypes.c_float, _c_int, _c_void_p], _c_int),
     "kgs_qknorm_rope_bwd_bf16": ([_c_void_p] * 11 + [_c_long] + [_c_int] * 3 + [_c_long] * 3 + [_c_int] * 2 +
                                  [ctypes.c_float, _c_int, _c_void_p], _c_int),
+    # mixture-of-experts routing (native/kernels/moe_route.hip)
+    "kgs_moe_workspace": ([_c_long, _c_int, _c_int], _c_long),
+    "kgs_moe_route_bf16": ([_c_void_p] * 7 + [_c_long] + [_c_int] * 3 + [_c_long, _c_void_p], _c_int),
+    "kgs_moe_route_bwd_bf16": ([_c_void_p] * 4 + [_c_long, _c_int, _c_int, _c_long, _c_void_p], _c_int),
+    "kgs_moe_gather_bf16": ([_c_void_p] * 4 + [_c_long, _c_long, _c_int, _c_int, _c_long, _c_long, _c_void_p], _c_int),
+    "kgs_moe_combine_bf16": ([_c_void_p] * 4 + [_c_long, _c_long, _c_int, _c_int, _c_long, _c_long, _c_void_p],
+                             _c_int),
+    "kgs_moe_combine_bwd_bf16": ([_c_void_p] * 7 + [_c_long, _c_long, _c_int, _c_int] + [_c_long] * 3 + [_c_void_p],
+                                 _c_int),
     # fp8 training producers (native/kernels/fp8_train.hip)
     "kgs_fp8_amax_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4, _c_int),
     "kgs_fp8_quant_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4 +
