@@ -43,6 +43,7 @@ without the window, and ``window=None`` is exactly the model without the option.
 ``top_k`` of them per token, on slabs of ``capacity_factor`` times the even share),
 in place of ``gate_up`` / ``down``: the kgs backend on the routing kernels of
 ``native/kernels/moe_route.hip``; ``experts=0`` is exactly the dense layer.
+``expert_gemm="batched"`` runs the experts on the batched GEMM of ``native/kernels/moe_gemm.hip``.
 The reference has no model code; nothing here is ported.
 """
 from __future__ import annotations
@@ -69,7 +70,7 @@ class DecoderLayer(torch.nn.Module):
                  causal: bool = True, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", qk_norm: bool = False,
                  qk_norm_eps: float = 1e-6, window: int | None = None, experts: int = 0, top_k: int = 2,
-                 capacity_factor: float = 1.25):
+                 capacity_factor: float = 1.25, expert_gemm: str = "loop"):
         super().__init__()
         if backend not in ("kgs", "torch"):
             raise ValueError(f"backend must be 'kgs' or 'torch', not {backend!r}")
@@ -128,7 +129,7 @@ class DecoderLayer(torch.nn.Module):
             from .moe import MoEFFN
 
             self.moe = MoEFFN(dim, inter, experts, top_k=top_k, capacity_factor=capacity_factor, backend=backend,
-                              device=device, dtype=dtype, seed=seed)
+                              device=device, dtype=dtype, seed=seed, expert_gemm=expert_gemm)
         else:
             self.gate_up, self.down = lin(dim, 2 * inter), lin(inter, dim)
         if self.qk_norm:  # registered last: the layer without them keeps its parameter order
@@ -220,7 +221,7 @@ class DecoderLM(torch.nn.Module):
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", embedding: str = "torch",
                  tie_embeddings: bool = False, qk_norm: bool = False, qk_norm_eps: float = 1e-6,
                  window: int | None = None, global_every: int = 0, experts: int = 0, top_k: int = 2,
-                 capacity_factor: float = 1.25):
+                 capacity_factor: float = 1.25, expert_gemm: str = "loop"):
         super().__init__()
         if global_every < 0:
             raise ValueError("global_every must be 0 (no global layers) or a positive layer period")
@@ -237,7 +238,8 @@ class DecoderLM(torch.nn.Module):
                          device=device, dtype=dtype, seed=seed + 1 + i, linear=linear, qk_norm=qk_norm,
                          qk_norm_eps=qk_norm_eps,
                          window=None if global_every > 0 and (i + 1) % global_every == 0 else window,
-                         experts=experts, top_k=top_k, capacity_factor=capacity_factor)
+                         experts=experts, top_k=top_k, capacity_factor=capacity_factor,
+                         expert_gemm=expert_gemm)
             for i in range(layers))
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:

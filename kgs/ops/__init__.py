@@ -33,6 +33,9 @@
   :func:`moe_combine_backward`, :func:`moe_route_backward` -- mixture-of-experts routing: top-k
   selection with softmax weights, fixed-capacity slots, the dispatch gather and the weighted
   combine, forward and backward (``native/kernels/moe_route.hip``)
+* :func:`moe_gemm`, :func:`ref_moe_gemm`, :func:`moe_linear` -- one batched GEMM over all experts'
+  capacity slabs that skips the empty rows, and the differentiable per-expert Linear on it
+  (``native/kernels/moe_gemm.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -85,7 +88,8 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         return mod if name == "qknorm_rope" else getattr(mod, name)
     if name in ("moe_route", "moe_route_backward", "moe_gather", "moe_combine", "moe_combine_backward", "moe_router",
                 "moe_dispatch", "Route", "ref_moe_route", "ref_moe_gather", "ref_moe_combine",
-                "ref_moe_dispatch_backward", "ref_moe_combine_backward", "ref_moe_route_backward"):
+                "ref_moe_dispatch_backward", "ref_moe_combine_backward", "ref_moe_route_backward", "moe_gemm",
+                "ref_moe_gemm", "moe_linear"):
         from . import moe
 
         return getattr(moe, name)

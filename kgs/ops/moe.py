@@ -1,8 +1,10 @@
 """Mixture-of-experts routing on the kernels of ``native/kernels/moe_route.hip``:
 top-k selection with softmax weights, token-priority slots on fixed-capacity
 slabs, the dispatch gather, the weighted combine, and their backwards. The FFNs
-run as the existing Linears on the row slices ``xe[e * C:(e + 1) * C]``, so every
-shape is static and a step is capturable in a graph.
+run as the existing Linears on the row slices ``xe[e * C:(e + 1) * C]``, or all at
+once on the batched GEMM of ``native/kernels/moe_gemm.hip`` (:func:`moe_gemm`,
+:func:`moe_linear`), which skips each slab's empty rows; either way every shape is
+static and a step is capturable in a graph.
 
 With ``logits [T, E]`` bf16 (``E`` a multiple of 8 in 8 .. 128), ``k = top_k`` in
 ``1 .. min(8, E)`` and ``C = capacity >= 1``::
@@ -308,6 +310,172 @@ def moe_combine(ye: torch.Tensor, route, weights: torch.Tensor | None = None) ->
     _check_rows(ye, "ye", route.src.numel())
     _on_gpu((ye, "ye"), (route.slot, "slot"), (route.weights, "weights"), (route.src, "src"))
     return _CombineFn.apply(ye, route.weights, route.slot, route.src)
+
+
+# ---------------------------------------------------------------------------
+# the batched expert GEMM (native/kernels/moe_gemm.hip)
+GEMM_BK = 64        # mode 2 runs whole K-steps of this many columns: [n_e, roundup(n_e, GEMM_BK)) is read
+MODES = {None: 0, "rows": 1, "reduce": 2}
+
+
+def _check_batched(t, name: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} must be a bf16 tensor")
+    if t.dim() != 3 or t.stride(2) != 1:
+        raise ValueError(f"{name} must be [E, rows, cols] with unit column stride")
+    if t.stride(1) < t.shape[2] or t.stride(1) % 8 or t.stride(0) < 0 or t.stride(0) % 8:
+        raise ValueError(f"{name}: the row stride must be a multiple of 8 elements, at least {t.shape[2]}, and the "
+                         "batch stride a non-negative multiple of 8")
+
+
+def _check_gemm(a, b, counts, mode, out) -> tuple:
+    if mode not in MODES:
+        raise ValueError(f"mode must be None, 'rows' or 'reduce', not {mode!r}")
+    _check_batched(a, "a")
+    _check_batched(b, "b")
+    (num, m, k), n = a.shape, b.shape[1]
+    if b.shape[0] != num or b.shape[2] != k or num < 1:
+        raise ValueError(f"a [E, M, K] and b [E, N, K] must agree in E and K, got {tuple(a.shape)}, {tuple(b.shape)}")
+    if m < 128 or n < 128 or k < 64 or m % 128 or n % 128 or k % GEMM_BK:
+        raise ValueError(f"M and N must be multiples of 128 and K of {GEMM_BK}, got M {m}, N {n}, K {k}")
+    if (counts is None) != (mode is None):
+        raise ValueError("counts and mode go together")
+    if counts is not None:
+        _check_table(counts, "counts", torch.int32, (num,))
+    if out is not None:
+        _check_batched(out, "out")
+        if tuple(out.shape) != (num, m, n):
+            raise ValueError(f"out must be {(num, m, n)}, got {tuple(out.shape)}")
+        if num > 1 and out.stride(0) < m * out.stride(1):  # a and b may overlap or repeat; outputs may not
+            raise ValueError(f"out: the batch stride must be at least M * the row stride, {m * out.stride(1)}")
+    return num, m, n, k
+
+
+def moe_gemm(a: torch.Tensor, b: torch.Tensor, counts: torch.Tensor | None = None, mode: str | None = None,
+             out: torch.Tensor | None = None, *, tile: int = -1) -> torch.Tensor:
+    """``out[e] = a[e] @ b[e].T`` for every e in one launch: bf16 ``a [E, M, K]``, ``b [E, N, K]``
+    -> ``[E, M, N]``, fp32 accumulation in ascending k, rounded once. Any row and batch
+    strides that are multiples of 8 elements (an operand may be a column block of a wider
+    matrix); ``M``, ``N`` multiples of 128, ``K`` of 64. ``counts`` (int32 ``[E]``, read on the
+    device) with ``n_e = clamp(counts[e], 0, limit)``:
+
+    * ``mode="rows"``, limit ``M``: rows ``m >= n_e`` of ``out[e]`` are zeros whatever ``a[e]`` holds
+      there, and tiles wholly past ``n_e`` do no work;
+    * ``mode="reduce"``, limit ``K``: the sum runs over ``k < roundup(n_e, GEMM_BK)`` only. Columns
+      past that are never read; those in ``[n_e, roundup(n_e, GEMM_BK))`` are, and the caller keeps
+      them zero (the dispatch and the combine's backward write zero rows there).
+
+    Every element of ``out`` is written; no atomics; bitwise repeatable; capturable. The slabs of
+    ``out`` must not overlap (batch stride at least ``M`` rows); those of ``a`` and ``b`` may.
+    ``tile`` is a measurement knob for the tile-shape A/B and the tests, not a tuning option: -1
+    (the default) takes 256 x 128 tiles with 3 stages where ``M % 256 == 0`` and 128 x 128 with 2
+    stages otherwise; 0 / 1 force the one or the other (1 needs ``M % 256 == 0``). Same bits either way."""
+    num, m, n, k = _check_gemm(a, b, counts, mode, out)
+    if tile not in (-1, 0, 1) or (tile == 1 and m % 256):
+        raise ValueError(f"tile must be -1, 0 or 1 (1 with M % 256 == 0 only), got {tile!r} with M {m}")
+    _on_gpu((a, "a"), (b, "b"), (counts, "counts"), (out, "out"))
+    _aligned((a, "a"), (b, "b"), (out, "out"))
+    if out is None:
+        out = torch.empty((num, m, n), dtype=torch.bfloat16, device=a.device)
+    rc = _lib.lib().kgs_moe_gemm_bf16_nt(a.data_ptr(), b.data_ptr(), out.data_ptr(),
+                                         0 if counts is None else counts.data_ptr(), num, m, n, k, a.stride(1),
+                                         b.stride(1), out.stride(1), a.stride(0), b.stride(0), out.stride(0),
+                                         MODES[mode], tile, _lib.stream_handle(a.device))
+    _lib.check(rc, f"moe_gemm[{num}x{m}x{n}x{k}, mode={mode}]")
+    return out
+
+
+def ref_moe_gemm(a, b, counts=None, mode=None, dtype=torch.float64):
+    """:func:`moe_gemm` in ``dtype``, unrounded: ``[E, M, N]``. ``"reduce"`` sums over ``k < n_e``, which
+    is the kernel's sum when the columns up to ``roundup(n_e, GEMM_BK)`` are zero. Differentiable."""
+    if mode not in MODES or (counts is None) != (mode is None):
+        raise ValueError("mode must be None, 'rows' or 'reduce', with counts exactly when it is not None")
+    a, b = a.to(dtype), b.to(dtype)
+    if mode == "reduce":
+        live = torch.arange(a.shape[2], device=a.device)[None, :] < counts.clamp(0, a.shape[2])[:, None]  # [E, K]
+        a = torch.where(live[:, None, :], a, torch.zeros_like(a))
+        b = torch.where(live[:, None, :], b, torch.zeros_like(b))
+    if mode == "rows":
+        live = torch.arange(a.shape[1], device=a.device)[None, :] < counts.clamp(0, a.shape[1])[:, None]  # [E, M]
+        a = torch.where(live[:, :, None], a, torch.zeros_like(a))
+    return a @ b.transpose(1, 2)
+
+
+def _stacked(weights) -> torch.Tensor:
+    """The E per-expert ``[N, K]`` weights as one ``[E, N, K]`` view; they must be consecutive
+    slices of one allocation."""
+    weights = list(weights)
+    if not weights:
+        raise ValueError("weights must hold at least one matrix")
+    w0 = weights[0]
+    for w in weights:
+        _bf16_matrix(w, "weights", tuple(w0.shape))
+    n, k = w0.shape
+    for i, w in enumerate(weights):
+        if not w.is_contiguous() or w.device != w0.device or \
+                w.untyped_storage().data_ptr() != w0.untyped_storage().data_ptr() or \
+                w.storage_offset() != w0.storage_offset() + i * n * k:
+            raise ValueError("weights must be consecutive contiguous slices of one [E, N, K] allocation (a MoEFFN with "
+                             "expert_gemm='batched' restacks its own on Module.to, not after load_state_dict(assign=True))")
+    return w0.detach().as_strided((len(weights), n, k), (n * k, k, 1))
+
+
+def _blocks(t: torch.Tensor, num: int) -> torch.Tensor:
+    """``[R, num * c]`` -> the ``num`` column blocks as a ``[num, R, c]`` view."""
+    c = t.shape[1] // num
+    return t.as_strided((num, t.shape[0], c), (c, t.stride(0), 1))
+
+
+def _slabs(t: torch.Tensor, num: int) -> torch.Tensor:
+    """``[num * C, cols]`` -> the ``num`` row slabs as a ``[num, C, cols]`` view."""
+    c = t.shape[0] // num
+    return t.as_strided((num, c, t.shape[1]), (c * t.stride(0), t.stride(0), 1))
+
+
+class _MoeLinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xe, counts, *weights):
+        w3 = _stacked(weights)
+        ctx.save_for_backward(xe, counts, w3)
+        return moe_gemm(_slabs(xe, w3.shape[0]), w3, counts, "rows").view(-1, w3.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .gemm import transpose
+
+        xe, counts, w3 = ctx.saved_tensors
+        num, n, k = w3.shape
+        dy = _grad_rows(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:  # dx_e = dy_e W_e: B the column block e of the stacked weights' transpose
+            wt = transpose(w3.view(num * n, k))  # [K, E N]
+            dx = moe_gemm(_slabs(dy, num), _blocks(wt, num), counts, "rows").view(-1, k)
+        if any(ctx.needs_input_grad[2:]):  # dW_e = dy_e^T x_e, summed over the filled rows only
+            dw = moe_gemm(_blocks(transpose(dy), num), _blocks(transpose(xe), num), counts, "reduce")
+        return (dx, None, *(dw.unbind(0) if dw is not None else (None,) * num))
+
+
+def moe_linear(xe: torch.Tensor, weights, counts: torch.Tensor) -> torch.Tensor:
+    """``ye[e C:(e + 1) C] = xe[e C:(e + 1) C] @ weights[e].T`` for the E slabs of ``xe [E C, K]`` in one
+    :func:`moe_gemm` launch (``"rows"``: rows past ``counts[e]`` give zero rows); differentiable in
+    ``xe`` and in the weights. The backward is two more launches and three 2-D transposes:
+    ``dx`` (``"rows"``) against the transposed stack, ``dW`` (``"reduce"`` over the filled rows, which
+    needs ``C % GEMM_BK == 0`` and the rows of ``xe`` and of the incoming gradient past
+    ``counts[e]`` to be zero, as :func:`moe_dispatch` and :func:`moe_combine` leave them). ``weights``:
+    the E ``[N, K]`` matrices, consecutive slices of one allocation (else ``ValueError``); their
+    gradients are views of one ``[E, N, K]`` buffer. ``N``, ``K`` and ``C`` multiples of 128."""
+    w3 = _stacked(weights)
+    num, n, k = w3.shape
+    _check_rows(xe, "xe", cols=k)
+    if xe.shape[0] % num:
+        raise ValueError(f"xe must be [E * C, {k}] with E = {num}, got {tuple(xe.shape)}")
+    _check_gemm(_slabs(xe, num), w3, counts, "rows", None)
+    if k % 128:
+        raise ValueError(f"K must be a multiple of 128 (it is the N of dx), got {k}")
+    _on_gpu((xe, "xe"), (w3, "weights"), (counts, "counts"))
+    if not _wants_grad(xe, *weights):
+        return moe_gemm(_slabs(xe, num), w3, counts, "rows").view(-1, n)
+    return _MoeLinearFn.apply(xe, counts, *weights)
 
 
 # ---------------------------------------------------------------------------
