@@ -44,6 +44,9 @@ without the window, and ``window=None`` is exactly the model without the option.
 in place of ``gate_up`` / ``down``: the kgs backend on the routing kernels of
 ``native/kernels/moe_route.hip``; ``experts=0`` is exactly the dense layer.
 ``expert_gemm="batched"`` runs the experts on the batched GEMM of ``native/kernels/moe_gemm.hip``.
+``DecoderLM(fused_loss=True)`` (kgs backend and glue, ``vocab % 128 == 0``) makes :meth:`DecoderLM.loss`
+the fused head + loss of ``native/kernels/linear_xent.hip``, :func:`kgs.ops.linear_cross_entropy`: the
+logits ``[tokens, vocab]`` and their gradient are never materialised; off, nothing changes.
 The reference has no model code; nothing here is ported.
 """
 from __future__ import annotations
@@ -214,14 +217,16 @@ class DecoderLM(torch.nn.Module):
     ``parameters()`` yields once (under ``embed.weight``); it takes the head's
     init, ``randn * dim ** -0.5``, and its gradient is the sum of the two uses'.
     ``window``, ``global_every``: sliding-window attention on every layer but each
-    ``global_every``-th (0: on every layer), see the module docstring."""
+    ``global_every``-th (0: on every layer), see the module docstring.
+    ``fused_loss``: :meth:`loss` runs the head and the cross-entropy in one kernel on the
+    normed hidden state and never holds the logits; :meth:`forward` still returns them."""
 
     def __init__(self, vocab: int, dim: int, layers: int, heads: int, kv_heads: int, inter: int, backend: str = "kgs",
                  glue: str | None = None, rope_theta: float = 10000.0, eps: float = 1e-5, device=None,
                  dtype=torch.bfloat16, seed: int = 0, linear: str = "bf16", embedding: str = "torch",
                  tie_embeddings: bool = False, qk_norm: bool = False, qk_norm_eps: float = 1e-6,
                  window: int | None = None, global_every: int = 0, experts: int = 0, top_k: int = 2,
-                 capacity_factor: float = 1.25, expert_gemm: str = "loop"):
+                 capacity_factor: float = 1.25, expert_gemm: str = "loop", fused_loss: bool = False):
         super().__init__()
         if global_every < 0:
             raise ValueError("global_every must be 0 (no global layers) or a positive layer period")
@@ -244,6 +249,9 @@ class DecoderLM(torch.nn.Module):
         self.backend, self.glue = backend, self.layers[0].glue if layers else (backend if glue is None else glue)
         if self.glue == "kgs" and vocab % 8:
             raise ValueError("the kgs loss takes a vocabulary that is a multiple of 8")
+        self.fused_loss = bool(fused_loss)
+        if self.fused_loss and (backend != "kgs" or self.glue != "kgs" or vocab % 128):
+            raise ValueError("fused_loss takes backend='kgs', the kgs glue and a vocabulary that is a multiple of 128")
         if embedding == "kgs":
             from kgs.ops.embedding import Embedding
 
@@ -266,8 +274,8 @@ class DecoderLM(torch.nn.Module):
         if tie_embeddings:
             self.head.weight = self.embed.weight
 
-    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
-        """``tokens``: int64 ``[batch, seq]`` -> logits ``[batch * seq, vocab]``."""
+    def _hidden(self, tokens: torch.Tensor) -> torch.Tensor:
+        """``tokens``: int64 ``[batch, seq]`` -> the normed hidden state ``[batch * seq, dim]``."""
         b, s = tokens.shape
         x, delta = self.embed(tokens), None
         for layer in self.layers:
@@ -277,15 +285,23 @@ class DecoderLM(torch.nn.Module):
         if self.glue == "kgs":
             from kgs.ops.transformer import rmsnorm_residual
 
-            h = rmsnorm_residual(x2, d2, self.norm, self.eps)[1]
-        else:
-            h = _torch_rmsnorm(x2 if d2 is None else x2 + d2, self.norm, self.eps)
-        return self.head(h)
+            return rmsnorm_residual(x2, d2, self.norm, self.eps)[1]
+        return _torch_rmsnorm(x2 if d2 is None else x2 + d2, self.norm, self.eps)
+
+    def forward(self, tokens: torch.Tensor) -> torch.Tensor:
+        """``tokens``: int64 ``[batch, seq]`` -> logits ``[batch * seq, vocab]``."""
+        return self.head(self._hidden(tokens))
 
     def loss(self, tokens: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         """Mean cross-entropy (fp32 scalar) of ``targets`` ``[batch, seq]``."""
-        logits, tg = self(tokens), targets.reshape(-1)
+        tg = targets.reshape(-1)
         live = (tg >= 0) & (tg < self.vocab)
+        if self.fused_loss:
+            from kgs.ops.linear_xent import linear_cross_entropy
+
+            rows = linear_cross_entropy(self._hidden(tokens), self.head.weight, tg.contiguous())
+            return rows.sum() / live.sum().clamp(min=1)
+        logits = self(tokens)
         if self.glue == "kgs":
             from kgs.ops.transformer import softmax_cross_entropy
 

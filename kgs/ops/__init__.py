@@ -36,6 +36,9 @@
 * :func:`moe_gemm`, :func:`ref_moe_gemm`, :func:`moe_linear` -- one batched GEMM over all experts'
   capacity slabs that skips the empty rows, and the differentiable per-expert Linear on it
   (``native/kernels/moe_gemm.hip``)
+* :func:`linear_cross_entropy` over :func:`linear_cross_entropy_rows` and :func:`linear_cross_entropy_dlogits`,
+  :func:`ref_linear_cross_entropy` -- the LM head fused with the softmax cross-entropy: the logits stay in
+  the MFMA accumulators, forward and backward (``native/kernels/linear_xent.hip``)
 
 Importing this package does not touch the GPU; the native library is loaded on
 first use and raises :class:`NativeUnavailable` if it is missing.
@@ -93,4 +96,9 @@ def __getattr__(name):  # lazy: keep `import kgs.ops` free of torch for CPU-only
         from . import moe
 
         return getattr(moe, name)
+    if name in ("linear_cross_entropy", "linear_cross_entropy_rows", "linear_cross_entropy_dlogits",
+                "ref_linear_cross_entropy"):
+        from . import linear_xent
+
+        return getattr(linear_xent, name)
     raise AttributeError(name)

@@ -124,6 +124,11 @@ _SIGS = {
                                  _c_int),
     # batched GEMM over MoE capacity slabs (native/kernels/moe_gemm.hip)
     "kgs_moe_gemm_bf16_nt": ([_c_void_p] * 4 + [_c_int] * 4 + [_c_long] * 6 + [_c_int, _c_int, _c_void_p], _c_int),
+    # fused LM head + cross-entropy (native/kernels/linear_xent.hip)
+    "kgs_linear_xent_workspace": ([_c_int, _c_int], _c_long),
+    "kgs_linear_xent_fwd_bf16": ([_c_void_p] * 6 + [_c_int] * 3 + [_c_long, _c_long, _c_int, _c_void_p], _c_int),
+    "kgs_linear_xent_dlogits_bf16": ([_c_void_p] * 6 + [_c_int] * 3 + [_c_long] * 3 + [_c_int] * 3 + [_c_void_p],
+                                     _c_int),
     # fp8 training producers (native/kernels/fp8_train.hip)
     "kgs_fp8_amax_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4, _c_int),
     "kgs_fp8_quant_bf16": ([_c_void_p, _c_int, _c_int, _c_long] + [_c_void_p] * 4 +
